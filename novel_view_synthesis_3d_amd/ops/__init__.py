@@ -67,15 +67,18 @@ def hip_available() -> bool:
     return mod is not None
 
 
+def _bf16_path(x: torch.Tensor) -> bool:
+    """The bf16 HIP kernels take x as it is or as autocast will cast it."""
+    return x.dtype == torch.bfloat16 or torch.is_autocast_enabled()
+
+
 # ---------------------------------------------------------------------------
 # Dispatched ops. Signatures match ops/reference.py.
 # ---------------------------------------------------------------------------
 
 def frame_conv3x3(x, weight, bias, stride: int = 1):
     if _use_hip(x, "frame_conv3x3"):
-        bf16_path = (x.dtype == torch.bfloat16
-                     or torch.is_autocast_enabled())
-        if bf16_path:  # MFMA igemm kernel or im2col+hipBLASLt — no MIOpen
+        if _bf16_path(x):  # MFMA igemm kernel or im2col+hipBLASLt — no MIOpen
             return _HIP_MOD.frame_conv3x3(x, weight, bias, stride)
     return ref.frame_conv3x3(x, weight, bias, stride)
 
@@ -94,14 +97,11 @@ def attention(q, k, v, kv_swap: bool = False):
     the model's cross-FRAME attention with both frames batched as (B*2)."""
     if _use_hip(q, "attention"):
         B, L, h, d = q.shape
-        bf16_path = (q.dtype == torch.bfloat16
-                     or torch.is_autocast_enabled())
-        if bf16_path and L % 64 == 0 and d in (16, 32, 64, 128, 256):
+        if _bf16_path(q) and L % 64 == 0 and d in (16, 32, 64, 128, 256):
             return _HIP_MOD.attention(q, k, v, kv_swap)
     if kv_swap:
-        B2 = k.shape[0]
-        k = k.reshape(B2 // 2, 2, *k.shape[1:]).flip(1).reshape(k.shape)
-        v = v.reshape(B2 // 2, 2, *v.shape[1:]).flip(1).reshape(v.shape)
+        k = ref.swap_frame_pairs(k)
+        v = ref.swap_frame_pairs(v)
     return ref.attention(q, k, v)
 
 
@@ -109,9 +109,7 @@ def linear(x, w, b=None):
     """nn.Linear forward; on MI355X the backward uses the split-K MFMA
     wgrad kernel for the tall-skinny shapes hipBLASLt collapses on."""
     if _use_hip(x, "linear"):
-        bf16_path = (x.dtype == torch.bfloat16
-                     or torch.is_autocast_enabled())
-        if bf16_path:
+        if _bf16_path(x):
             return _HIP_MOD.linear(x, w, b)
     import torch.nn.functional as F
     return F.linear(x, w, b)
@@ -138,9 +136,7 @@ def residual_scale_add(h, h_in):
 def frame_conv3x3_residual(x, weight, bias, residual, res_scale: float):
     """Fused ResnetBlock tail: (conv(x,w)+bias+residual)*res_scale."""
     if _use_hip(x, "frame_conv3x3"):
-        bf16_path = (x.dtype == torch.bfloat16
-                     or torch.is_autocast_enabled())
-        if bf16_path:
+        if _bf16_path(x):
             return _HIP_MOD.frame_conv3x3_residual(x, weight, bias,
                                                    residual, res_scale)
     y = ref.frame_conv3x3(x, weight, bias, 1)

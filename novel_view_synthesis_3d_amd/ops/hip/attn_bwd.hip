@@ -30,10 +30,6 @@
 
 namespace {
 
-using bf16 = __hip_bfloat16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 struct ABwdShape {
   int B, L, H, D;
   int Lk;
@@ -44,11 +40,6 @@ struct ABwdShape {
   int kv_swap;     // batch b's queries attend batch b^1's k/v (batched
                    // cross-frame attention; see attn_fwd.hip)
 };
-
-__device__ __forceinline__ int swz_row(int row, int byte_in_row,
-                                       int row_bytes) {
-  return (row * row_bytes + byte_in_row) ^ ((row & 7) << 4);
-}
 
 // ---------------------------------------------------------------------------
 // delta[b,l,h] = sum_d do * o   (both (B,L,H,D) bf16 contiguous)

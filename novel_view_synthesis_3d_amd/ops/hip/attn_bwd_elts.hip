@@ -14,8 +14,6 @@
 
 namespace {
 
-using bf16 = __hip_bfloat16;
-
 // p[b,h,i,j] = exp(s[b,h,i,j]*scale - lse[b,i,h])
 __global__ void attn_p_kernel(const bf16* __restrict__ s,
                               const float* __restrict__ lse,  // (B,L,H)

@@ -26,10 +26,6 @@
 
 namespace {
 
-using bf16 = __hip_bfloat16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 constexpr int QB = 16;     // q rows per wave
 constexpr int KB = 64;     // keys per tile
 constexpr int WAVES = 4;   // q rows per block = 64
@@ -47,11 +43,6 @@ struct AttnShape {
   int kv_swap;          // batch b attends to k/v of batch b^1 (the model's
                         // cross-FRAME attention with both frames batched)
 };
-
-__device__ __forceinline__ int swz_row(int row, int byte_in_row,
-                                       int row_bytes) {
-  return (row * row_bytes + byte_in_row) ^ ((row & 7) << 4);
-}
 
 template <int D>
 __global__ __launch_bounds__(256)

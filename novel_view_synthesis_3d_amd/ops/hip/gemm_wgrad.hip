@@ -31,29 +31,6 @@
 
 namespace {
 
-using bf16 = __hip_bfloat16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using as3_bf16x4p = __attribute__((address_space(3))) bf16x4*;
-
-using as1_cvp = const __attribute__((address_space(1))) void*;
-using as3_vp = __attribute__((address_space(3))) void*;
-__device__ __forceinline__ as1_cvp as_global(const void* p) {
-  return (as1_cvp)(unsigned long long)(uintptr_t)p;
-}
-__device__ __forceinline__ as3_vp as_shared(void* p) {
-  return (as3_vp)(unsigned int)(uintptr_t)p;
-}
-
-__device__ __forceinline__ bf16x8 tr16x8w(const char* p0, const char* p1) {
-  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (as3_bf16x4p)(const_cast<char*>(p0)));
-  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (as3_bf16x4p)(const_cast<char*>(p1)));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 constexpr int LBN = 256;   // n per block tile
 constexpr int LBK = 256;   // k per block tile
 constexpr int LWT = 512;   // 8 waves
@@ -186,7 +163,7 @@ void linear_wgrad_kernel(const bf16* __restrict__ dy,   // (M, N)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const char* pa = dyb + p0 * LROW + (wn * 64 + i * 32) * 2;
-          af[i] = tr16x8w(pa, pa + 4 * LROW);
+          af[i] = tr16x8(pa, pa + 4 * LROW);
         }
         if (do_bias) {
 #pragma unroll
@@ -198,7 +175,7 @@ void linear_wgrad_kernel(const bf16* __restrict__ dy,   // (M, N)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const char* pb = xb + p0 * LROW + (wk * 128 + j * 32) * 2;
-            bf16x8 bf = tr16x8w(pb, pb + 4 * LROW);
+            bf16x8 bf = tr16x8(pb, pb + 4 * LROW);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
               *reinterpret_cast<f32x16*>(acc[i * 4 + j]) =

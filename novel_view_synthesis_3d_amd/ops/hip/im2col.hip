@@ -14,8 +14,6 @@
 
 namespace {
 
-using bf16 = __hip_bfloat16;
-
 // m indexes the OUTPUT grid (IMG, Ho, Wo); input pixel = out*stride + d - pad
 // nplanes == 9: full (dy,dx) window; nplanes == 3: row-shift only
 // (dy in {-1,0,1}, dx = 0 — the wgrad 3-row-shift decomposition)

@@ -12,8 +12,6 @@
 
 namespace {
 
-using bf16 = __hip_bfloat16;
-
 // out = nearest-2x of in; pack index over OUTPUT (coalesced stores)
 template <typename T>
 __global__ void up2x_kernel(const T* __restrict__ in, T* __restrict__ out,

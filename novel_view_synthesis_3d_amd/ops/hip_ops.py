@@ -12,6 +12,7 @@ from typing import Optional
 import torch
 
 from novel_view_synthesis_3d_amd.ops.build import built_path
+from novel_view_synthesis_3d_amd.ops.reference import swap_frame_pairs
 
 _SO = built_path()
 if not os.path.exists(_SO):
@@ -30,8 +31,8 @@ HAS = {"joint_groupnorm", "pose_embedding", "frame_conv3x3", "attention",
 
 def conv_shapes_supported(cin: int, cout: int, stride: int) -> bool:
     """The implicit-GEMM kernel covers the FLOP-dominant convs (stride 1,
-    Cin%64==0, Cout%128==0); stem (3ch), pose-emb (144ch), head (3ch) and
-    small-config convs take the MIOpen path."""
+    Cin%64==0, Cout%128==0); stem (3ch), strided pose-emb (144ch), head
+    (3ch) and small-config convs take the im2col + hipBLASLt GEMM route."""
     return stride == 1 and cin % 64 == 0 and cout % 128 == 0
 
 
@@ -157,9 +158,21 @@ def fused_adam_step(plan: AdamPlan, lr, b1, b2, eps, step: int) -> None:
 
 
 # ---------------------------------------------------------------------------
-# Implicit-GEMM 3x3 conv (K1): fwd + dgrad on the MFMA kernel, wgrad via
-# MIOpen convolution_backward (library path for the long-K reduction GEMM).
+# 3x3 conv (K1): fwd + dgrad on the implicit-GEMM MFMA kernel, wgrad on the
+# direct MFMA wgrad kernel; shapes those kernels do not cover go through
+# im2col + hipBLASLt GEMMs. MIOpen is used nowhere.
 # ---------------------------------------------------------------------------
+
+def _conv_dgrad(dy, w):
+    """dx of a stride-1 conv: conv3x3(dy, w~) with
+    w~[ci,ey,ex,co] = w[co,2-ey,2-ex,ci], on the MFMA kernel when it covers
+    the transposed shape, else by im2col of dy + one GEMM."""
+    cout, _, _, cin = w.shape
+    wt = torch.flip(w, dims=(1, 2)).permute(3, 1, 2, 0).contiguous()
+    if conv_shapes_supported(cout, cin, 1):
+        return _OPS.conv3x3_fwd(dy, wt, None, None, 1.0)
+    return _gemm_conv_fwd(dy, wt, None, 1)
+
 
 class _FrameConv3x3(torch.autograd.Function):
     """MFMA igemm conv with an optionally fused residual tail:
@@ -187,39 +200,17 @@ class _FrameConv3x3(torch.autograd.Function):
         dy = dy.contiguous()
         if ctx.res_scale != 1.0:
             dy = dy * ctx.res_scale
-        cout, _, _, cin = w.shape
         need_x, need_w, need_b = (ctx.needs_input_grad[0],
                                   ctx.needs_input_grad[1], ctx.has_bias)
         dx = dw = db = None
         if need_x:
-            # dgrad = conv3x3(dy, w~), w~[ci,ey,ex,co] = w[co,2-ey,2-ex,ci]
-            wt = torch.flip(w, dims=(1, 2)).permute(3, 1, 2, 0).contiguous()
-            if conv_shapes_supported(cout, cin, 1):
-                dx = _OPS.conv3x3_fwd(dy, wt, None, None, 1.0)
-            else:
-                dx = _miopen_conv(dy, wt, None)
+            dx = _conv_dgrad(dy, w)
         if need_w or need_b:
             dw4, db = _wgrad(x, w, dy, ctx.has_bias)
             if need_w:
                 dw = dw4
         dres = dy if ctx.has_res else None
         return dx, dw, db, dres, None
-
-
-def _nchw_view(x5):
-    """(IMG,H,W,C) or (B,F,H,W,C) contiguous -> NCHW channels_last view."""
-    if x5.dim() == 5:
-        B, F, H, W, C = x5.shape
-        x5 = x5.reshape(B * F, H, W, C)
-    return x5.permute(0, 3, 1, 2)
-
-
-def _miopen_conv(x, w, bias):
-    import torch.nn.functional as Fn
-    shape = x.shape
-    y = Fn.conv2d(_nchw_view(x), w.permute(0, 3, 1, 2), bias, padding=1)
-    out = y.permute(0, 2, 3, 1)
-    return out.reshape(*shape[:-1], w.shape[0]).contiguous()
 
 
 def _wgrad_shapes_supported(x, cout) -> bool:
@@ -290,12 +281,11 @@ def _wgrad_im2col_gemm(x, w, dy, has_bias):
 
 def _pad_c8(t):
     """Pad the channel (last) dim to a multiple of 8 (im2col needs 16B packs)."""
-    c = t.shape[-1]
-    pad = (-c) % 8
+    pad = (-t.shape[-1]) % 8
     if pad == 0:
-        return t, c
+        return t
     import torch.nn.functional as Fn
-    return Fn.pad(t, (0, pad)), c
+    return Fn.pad(t, (0, pad))
 
 
 def _gemm_conv_fwd(x, w, bias, stride):
@@ -303,7 +293,7 @@ def _gemm_conv_fwd(x, w, bias, stride):
     (stem 3ch, pose-emb 144ch strided, head 3ch, small configs): strided
     im2col kernel + ONE hipBLASLt GEMM. Replaces MIOpen entirely."""
     cout, _, _, cin = w.shape
-    xp, _ = _pad_c8(x.contiguous())
+    xp = _pad_c8(x.contiguous())
     A = _OPS.im2col3x3(xp, stride, 9, 0, -1, None)          # (Mo, 9*Cpad)
     cpad = xp.shape[-1]
     w2 = w.permute(1, 2, 3, 0)                            # (3,3,Cin,Cout)
@@ -343,18 +333,15 @@ class _FrameConvGeneric(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             assert ctx.stride == 1, "strided dgrad not needed by the model"
-            wt = torch.flip(w, dims=(1, 2)).permute(3, 1, 2, 0).contiguous()
-            if conv_shapes_supported(cout, cin, 1):
-                dx = _OPS.conv3x3_fwd(dy, wt, None, None, 1.0)
-            else:
-                dx = _gemm_conv_fwd(dy, wt, None, 1)
+            dx = _conv_dgrad(dy, w)
         if ctx.needs_input_grad[1] or ctx.has_bias:
             dyf = dy.reshape(-1, cout)
-            xp, _ = _pad_c8(x)
+            xp = _pad_c8(x)
             cpad = xp.shape[-1]
             A = _OPS.im2col3x3(xp, ctx.stride, 9, 0, -1, None)
             dwf = torch.matmul(A.transpose(0, 1), dyf)    # (9*Cpad, Cout)
-            dw = dwf.reshape(3, 3, cpad, cout)[:, :, :cin, :]                 .permute(3, 0, 1, 2).contiguous()
+            dw = (dwf.reshape(3, 3, cpad, cout)[:, :, :cin, :]
+                  .permute(3, 0, 1, 2).contiguous())
             if not ctx.needs_input_grad[1]:
                 dw = None
             db = (dyf.sum(0, dtype=torch.float32).to(dy.dtype)
@@ -378,17 +365,20 @@ def frame_conv3x3(x, weight, bias, stride: int = 1):
     return _FrameConvGeneric.apply(x, weight, bias, stride)
 
 
+def frame_conv3x3_residual(x, weight, bias, residual, res_scale):
+    """y = (conv3x3(x,w) + bias + residual) * res_scale, residual fused in
+    the conv epilogue when the MFMA kernel covers the shape."""
+    cout, _, _, cin = weight.shape
+    if conv_shapes_supported(cin, cout, 1):
+        return _FrameConv3x3.apply(x, weight, bias, residual, res_scale)
+    y = frame_conv3x3(x, weight, bias, 1)
+    return (y + residual) * res_scale
+
+
 # ---------------------------------------------------------------------------
 # Flash MFMA attention (K7): HIP forward (saves logsumexp), GEMM-recompute
 # backward (rocBLAS batched matmuls — the "plain library GEMM" path).
 # ---------------------------------------------------------------------------
-
-def _swap_frame_pairs(t):
-    """(2B', ...) -> pairs (2i, 2i+1) exchanged (cross-frame kv order)."""
-    B2 = t.shape[0]
-    return (t.reshape(B2 // 2, 2, *t.shape[1:]).flip(1)
-            .reshape(t.shape).contiguous())
-
 
 class _Attention(torch.autograd.Function):
     @staticmethod
@@ -425,8 +415,8 @@ class _Attention(torch.autograd.Function):
         if swap:
             # GEMM-recompute fallback shapes (d=256 / short L): materialize
             # the frame swap, then un-swap the kv grads
-            k = _swap_frame_pairs(k)
-            v = _swap_frame_pairs(v)
+            k = swap_frame_pairs(k).contiguous()
+            v = swap_frame_pairs(v).contiguous()
         scale = 1.0 / (D ** 0.5)
         # (B,H,L,D) strided views; rocBLAS consumes them without copies
         qt = q.permute(0, 2, 1, 3)
@@ -446,8 +436,8 @@ class _Attention(torch.autograd.Function):
         dk = dk.permute(0, 2, 1, 3).contiguous()
         dv = dv.permute(0, 2, 1, 3).contiguous()
         if swap:
-            dk = _swap_frame_pairs(dk)
-            dv = _swap_frame_pairs(dv)
+            dk = swap_frame_pairs(dk).contiguous()
+            dv = swap_frame_pairs(dv).contiguous()
         return dq, dk, dv, None
 
 
@@ -506,16 +496,6 @@ class _LinearFn(torch.autograd.Function):
 
 def linear(x, w, b=None):
     return _LinearFn.apply(x, w, b)
-
-
-def frame_conv3x3_residual(x, weight, bias, residual, res_scale):
-    """y = (conv3x3(x,w) + bias + residual) * res_scale, residual fused in
-    the conv epilogue when the MFMA kernel covers the shape."""
-    cout, _, _, cin = weight.shape
-    if conv_shapes_supported(cin, cout, 1):
-        return _FrameConv3x3.apply(x, weight, bias, residual, res_scale)
-    y = frame_conv3x3(x, weight, bias, 1)
-    return (y + residual) * res_scale
 
 
 # ---------------------------------------------------------------------------

@@ -102,6 +102,13 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor
     return out.permute(0, 2, 1, 3)
 
 
+def swap_frame_pairs(t: torch.Tensor) -> torch.Tensor:
+    """(2B', ...) -> batch entries (2i, 2i+1) exchanged: the k/v order of the
+    model's cross-frame attention with both frames batched."""
+    B2 = t.shape[0]
+    return t.reshape(B2 // 2, 2, *t.shape[1:]).flip(1).reshape(t.shape)
+
+
 def nearest_upsample2x(x: torch.Tensor) -> torch.Tensor:
     """K8: nearest-neighbor 2x upsample (/root/reference/model/xunet.py:14-18)."""
     B, Fr, H, W, C = x.shape

@@ -167,6 +167,7 @@ CONV_SHAPES = [
     (1, 2, 16, 16, 768, 128),
     (1, 2, 8, 8, 1024, 512),
     (1, 2, 32, 32, 64, 128),   # small-ish, W=32
+    (1, 3, 8, 8, 64, 128),     # M=192: the second 128-row block is half empty
 ]
 
 
@@ -179,16 +180,24 @@ def test_conv3x3_forward_parity(shape):
     w = torch.randn(Cout, 3, 3, Cin, device="cuda", generator=g,
                     dtype=torch.bfloat16) * (1.0 / (3 * Cin ** 0.5))
     b = torch.randn(Cout, device="cuda", generator=g) * 0.1
+    r = torch.randn(B, F, H, W, Cout, device="cuda", generator=g,
+                    dtype=torch.bfloat16)
     got = torch.ops.nvs3d.conv3x3_fwd(x, w, b, None, 1.0)
     want = ref.frame_conv3x3(x.float(), w.float(), b.float())
     err = (got.float() - want).abs().max().item()
     scale = want.abs().max().item()
     assert err < 3e-2 * max(scale, 1.0), (err, scale)
+    # fused residual tail (the epilogue shared with the 256-tile kernel)
+    got2 = torch.ops.nvs3d.conv3x3_fwd(x, w, b, r, 1.0 / math.sqrt(2))
+    want2 = (want + r.float()) / math.sqrt(2)
+    err2 = (got2.float() - want2).abs().max().item()
+    assert err2 < 3e-2 * max(want2.abs().max().item(), 1.0), err2
 
 
-def test_conv3x3_autograd_parity():
-    B, F, H, W, Cin, Cout = 1, 2, 16, 16, 256, 128
-    g = torch.Generator(device="cuda").manual_seed(1)
+def _conv_autograd_parity(shape, seed):
+    """y/dx/dw/db of hip_ops.frame_conv3x3 (bf16) vs the fp32 oracle."""
+    B, F, H, W, Cin, Cout = shape
+    g = torch.Generator(device="cuda").manual_seed(seed)
     x0 = torch.randn(B, F, H, W, Cin, device="cuda", generator=g,
                      dtype=torch.bfloat16)
     w0 = torch.randn(Cout, 3, 3, Cin, device="cuda", generator=g,
@@ -209,9 +218,27 @@ def test_conv3x3_autograd_parity():
     want = run(lambda x, w, b: ref.frame_conv3x3(x, w, b), torch.float32)
     names = ["y", "dx", "dw", "db"]
     for n, gg, ww in zip(names, got, want):
+        assert gg.shape == ww.shape, (n, gg.shape, ww.shape)
         err = (gg - ww).abs().max().item()
         scale = ww.abs().max().item() + 1e-6
         assert err / scale < 5e-2, f"{n}: rel {err/scale:.3e}"
+
+
+def test_conv3x3_autograd_parity():
+    _conv_autograd_parity((1, 2, 16, 16, 256, 128), seed=1)
+
+
+@pytest.mark.parametrize("shape", [
+    # Cin=64: dgrad's transposed shape (Cout'=64) is not covered by the MFMA
+    # kernel -> im2col of dy + GEMM. W=8: wgrad takes the im2col fallback.
+    (1, 2, 8, 8, 64, 128),
+    (1, 2, 16, 16, 64, 128),    # same dgrad route, MFMA wgrad kernel
+    # Cin=144 stride 1: channels zero-padded to 192 into the MFMA kernels;
+    # dx / dw must come back unpadded
+    (1, 2, 16, 16, 144, 128),
+])
+def test_conv3x3_autograd_routes(shape):
+    _conv_autograd_parity(shape, seed=11)
 
 
 WGRAD_SHAPES = [
