@@ -179,3 +179,253 @@ class DDPMSampler:
             self._step(z, idx, cond2, mask, tab, pose_cache)
         for _ in range(self.num_steps - done_warmup):
             graph.replay()
+
+
+# ---------------------------------------------------------------------------
+# Stochastic conditioning (3DiM, arXiv:2210.04628 §2.2): multi-view sampling
+# ---------------------------------------------------------------------------
+
+class PoseFeatureBank:
+    """Pose cache handed to XUNet.forward by the stochastic sampler.
+
+    Holds, per resolution level, the source-frame features of every bank
+    view, the null (unconditional) source feature and the current target's
+    features; `emb` is the fused gather + logsnr add + SiLU. The index of
+    the conditioning view is derived on the device from (u, step, k), so the
+    object — and a graph captured through it — serves every step and view."""
+
+    def __init__(self, src, null, tgt, u, step, k):
+        self.src, self.null, self.tgt = src, null, tgt
+        self.u, self.step, self.k = u, step, k
+
+    def emb(self, level: int, logsnr_emb: torch.Tensor) -> torch.Tensor:
+        from novel_view_synthesis_3d_amd import ops
+        return ops.cond_emb_select(logsnr_emb, self.src[level],
+                                   self.null[level], self.tgt[level],
+                                   self.u, self.step, self.k)
+
+
+class StochasticConditioningSampler:
+    """Generate N target views one after another from one input view. At
+    every denoising step of a view the conditioning view is drawn uniformly
+    from the bank: the input plus every view generated so far.
+
+    The draw is `ops.stochastic_index(u[step], k)` on a table of uniforms
+    pre-drawn per view, so the step holds no host decision and no RNG op for
+    the index: eager and hipGraph replay see the same index sequence, and
+    one captured step serves all N*S steps.
+
+    Bank memory: per level Kcap*B*H'*W'*E*itemsize bytes (bf16 under
+    autocast), plus Kcap*B*H*W*3*4 for the images; Kcap = 1+N, or `max_bank`
+    (then the bank is a ring over the most recent views)."""
+
+    def __init__(self, model, schedule: Optional[DiffusionSchedule] = None,
+                 legacy_logsnr: bool = False, autocast: bool = True,
+                 max_bank: Optional[int] = None):
+        self.model = model
+        self.schedule = schedule or DiffusionSchedule(1000)
+        self.legacy_logsnr = legacy_logsnr
+        self.autocast = autocast
+        assert max_bank is None or max_bank >= 1
+        self.max_bank = max_bank
+        self.num_captures = 0       # graphs captured by the last call
+        self.index_log = []         # per view: (S,B) bank indices drawn
+        self.state = None           # buffers of the last call
+
+    # -----------------------------------------------------------------
+    def _ctx(self, device):
+        if device.type == "cuda" and self.autocast:
+            return torch.autocast("cuda", dtype=torch.bfloat16)
+        import contextlib
+        return contextlib.nullcontext()
+
+    def _step(self, st) -> None:
+        """One in-place ancestral step on st["z"]; everything device-side."""
+        from novel_view_synthesis_3d_amd import ops
+        z, tab = st["z"], st["tab"]
+        B = z.shape[0]
+        batch = {"x": st["x2"], "z": torch.cat([z, z], dim=0),
+                 "logsnr": tab["logsnr"].index_select(
+                     0, st["step"]).expand(2 * B)}
+        with self._ctx(z.device):
+            out = self.model(batch, st["mask"], pose_cache=st["cache"])
+        noise = torch.randn_like(z)
+        ops.ddpm_cfg_step(z, out, noise, tab["sqrt_recip_abar"],
+                          tab["sqrt_recipm1_abar"], tab["mean_c1"],
+                          tab["mean_c2"], tab["sigma"], st["step"], st["u"],
+                          st["k"], st["bank_img"], st["x2"], st["w"],
+                          st["clip"], st["noise_scale"],
+                          step_scratch=st["step_scratch"])
+
+    def _frame_features(self, st, R, t, frame):
+        cp = self.model.ConditioningProcessor_0
+        H, W = st["z"].shape[1:3]
+        with self._ctx(R.device):
+            return cp.frame_pose_features(R, t, st["K"], frame, H, W)
+
+    def _append(self, st, img, R, t) -> None:
+        """Add a finished (or the input) view to the bank and bump k."""
+        slot = st["count"] % st["Kcap"]
+        st["bank_img"][slot].copy_(img)
+        feats, _ = self._frame_features(st, R, t, 0)
+        for lvl, f in enumerate(feats):
+            st["cache"].src[lvl][slot].copy_(f)
+        st["count"] += 1
+        st["k"].fill_(min(st["count"], st["Kcap"]))
+
+    def _begin_view(self, st, R, t, z0, u) -> None:
+        """Reset the per-view state in place (static buffers)."""
+        from novel_view_synthesis_3d_amd import ops
+        B = z0.shape[0]
+        st["z"].copy_(z0)
+        st["step"].zero_()
+        st["u"].copy_(u)
+        feats, null = self._frame_features(st, R, t, 1)
+        for lvl, (f, nf) in enumerate(zip(feats, null)):
+            tgt = st["cache"].tgt[lvl]
+            tgt[:B].copy_(f)
+            tgt[B:].copy_(nf.expand_as(f))
+        idx = ops.stochastic_index(st["u"], st["k"])         # (S,B)
+        self.index_log.append(idx)
+        first = st["bank_img"][idx[0], torch.arange(B, device=idx.device)]
+        st["x2"][:B].copy_(first)
+        st["x2"][B:].copy_(first)
+
+    def _run_view(self, st, use_graph: bool) -> None:
+        S = st["S"]
+        if not use_graph:
+            for _ in range(S):
+                self._step(st)
+            return
+        remaining = S
+        cur = torch.cuda.current_stream()
+        if st["graph"] is None:
+            # warm up at most S steps on a side stream (required before
+            # capture); they are real steps of this view
+            n_warm = min(2, S)
+            gs = st["stream"] = torch.cuda.Stream()
+            gs.wait_stream(cur)
+            with torch.cuda.stream(gs):
+                for _ in range(n_warm):
+                    self._step(st)
+            cur.wait_stream(gs)
+            remaining -= n_warm
+            if remaining <= 0:
+                return  # nothing left to replay: a graph would be pointless
+            graph = torch.cuda.CUDAGraph()
+            # capture on the warm-up stream and replay there too (as the
+            # trainer does): a graph replayed on another stream than its
+            # capture stream was seen to race with out-of-graph work queued
+            # around back-to-back replays
+            with torch.cuda.graph(graph, stream=gs):
+                # capture records the step without executing it
+                self._step(st)
+            st["graph"] = graph
+            self.num_captures += 1
+        gs = st["stream"]
+        gs.wait_stream(cur)
+        with torch.cuda.stream(gs):
+            for _ in range(remaining):
+                st["graph"].replay()
+        cur.wait_stream(gs)
+
+    # -----------------------------------------------------------------
+    @torch.no_grad()
+    def sample_views(self, x0: torch.Tensor, R0: torch.Tensor,
+                     t0: torch.Tensor, K: torch.Tensor,
+                     target_R: torch.Tensor, target_t: torch.Tensor, *,
+                     num_steps: int, guidance_weight: float = 3.0,
+                     clip_denoised: bool = True, noise_scale: float = 1.0,
+                     seed: Optional[int] = None,
+                     z_init: Optional[torch.Tensor] = None,
+                     use_graph: bool = False, stochastic: bool = True,
+                     on_view_start=None) -> torch.Tensor:
+        """x0 (B,H,W,3) input view with pose R0 (B,3,3), t0 (B,3); K
+        (B,3,3); target_R (N,B,3,3), target_t (N,B,3). Returns (N,B,H,W,3).
+
+        `seed` seeds the generator of the conditioning-view draws only; z
+        and the step noise come from the global RNG exactly as in
+        DDPMSampler. `z_init` is (B,H,W,3) (used for every view) or
+        (N,B,H,W,3). `stochastic=False` always conditions on the input
+        view. `on_view_start(n, state)` runs after view n's state is set."""
+        model = self.model
+        was_training = model.training
+        model.eval()
+        try:
+            device = x0.device
+            N, B = target_R.shape[:2]
+            H, W = x0.shape[1:3]
+            S = num_steps
+            Kcap = 1 + N if self.max_bank is None else min(1 + N,
+                                                           self.max_bank)
+            if not stochastic and Kcap < 1 + N:
+                # ring bank: the input view would be evicted
+                raise ValueError("stochastic=False needs the input view to "
+                                 "stay in the bank (max_bank too small)")
+            helper = DDPMSampler(model, self.schedule, num_steps=S,
+                                 legacy_logsnr=self.legacy_logsnr)
+            cfg = model.cfg
+            E, L = cfg.emb_ch, cfg.num_resolutions
+            act = (torch.bfloat16 if device.type == "cuda" and self.autocast
+                   else torch.float32)
+            f32 = dict(dtype=torch.float32, device=device)
+
+            def lvl_hw(i):  # 'SAME' strided conv output size
+                return -(-H // 2 ** i), -(-W // 2 ** i)
+
+            step = torch.zeros(1, dtype=torch.long, device=device)
+            k = torch.zeros(1, dtype=torch.long, device=device)
+            u = torch.zeros(S, B, **f32)
+            cache = PoseFeatureBank(
+                src=[torch.zeros(Kcap, B, *lvl_hw(i), E, dtype=act,
+                                 device=device) for i in range(L)],
+                null=None,
+                tgt=[torch.zeros(2 * B, *lvl_hw(i), E, dtype=act,
+                                 device=device) for i in range(L)],
+                u=u, step=step, k=k)
+            st = {
+                "S": S, "Kcap": Kcap, "count": 0, "graph": None,
+                "w": float(guidance_weight), "clip": bool(clip_denoised),
+                "noise_scale": float(noise_scale),
+                "tab": helper._step_tables(device), "K": K,
+                "z": torch.zeros(B, H, W, 3, **f32),
+                "x2": torch.zeros(2 * B, H, W, 3, **f32),
+                "mask": torch.cat([torch.ones(B, device=device),
+                                   torch.zeros(B, device=device)]),
+                "bank_img": torch.zeros(Kcap, B, H, W, 3, **f32),
+                "step": step, "step_scratch": torch.zeros_like(step),
+                "k": k, "u": u, "cache": cache,
+            }
+            # the null source feature is camera-independent: computed once
+            _, null0 = self._frame_features(st, R0, t0, 0)
+            cache.null = [nf.contiguous() for nf in null0]
+            self.state, self.index_log, self.num_captures = st, [], 0
+
+            self._append(st, x0, R0, t0)
+            gen = torch.Generator()  # host generator: same u on any device
+            if seed is None:
+                gen.seed()
+            else:
+                gen.manual_seed(int(seed))
+            outs = torch.empty(N, B, H, W, 3, **f32)
+            for n in range(N):
+                if z_init is None:
+                    z0 = torch.empty_like(x0).normal_()
+                else:
+                    z0 = z_init if z_init.dim() == 4 else z_init[n]
+                if stochastic:
+                    un = torch.rand(S, B, generator=gen)
+                else:
+                    un = torch.zeros(S, B)
+                self._begin_view(st, target_R[n], target_t[n], z0,
+                                 un.to(device))
+                if on_view_start is not None:
+                    on_view_start(n, st)
+                self._run_view(st, use_graph and device.type == "cuda")
+                outs[n].copy_(st["z"])
+                if n + 1 < N:
+                    self._append(st, st["z"].clamp(-1.0, 1.0), target_R[n],
+                                 target_t[n])
+            return outs
+        finally:
+            model.train(was_training)

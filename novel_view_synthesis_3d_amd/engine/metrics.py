@@ -44,3 +44,13 @@ class JsonlLogger:
     def close(self) -> None:
         if self.enabled:
             self._f.close()
+
+
+def psnr(pred, target, data_range: float = 2.0) -> float:
+    """Peak signal-to-noise ratio in dB of two images (any shape, torch
+    tensors); `data_range` is max - min of the value range ([-1,1] -> 2)."""
+    import math
+    mse = float(((pred.float() - target.float()) ** 2).mean())
+    if mse == 0.0:
+        return float("inf")
+    return 10.0 * math.log10(data_range ** 2 / mse)

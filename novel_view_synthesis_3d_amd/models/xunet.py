@@ -96,6 +96,37 @@ class ConditioningProcessor(nn.Module):
         return [getattr(self, f"Conv_{i}")(pose_emb)
                 for i in range(cfg.num_resolutions)]
 
+    def frame_pose_features(self, R: torch.Tensor, t: torch.Tensor,
+                            K: torch.Tensor, frame: int, H: int, W: int):
+        """Per-level pose features of ONE frame slot (0 = source, 1 = target)
+        for camera (R (B,3,3), t (B,3), K (B,3,3)).
+
+        FrameConv is per frame, so these equal that frame's slice of
+        `pose_features`. Returns (unmasked, masked): per-level lists of
+        (B,H',W',E) and (1,H',W',E). The masked (cond_mask=0) features see a
+        zero pose embedding, hence depend on no camera: one row serves every
+        batch element and every view."""
+        cfg = self.cfg
+        emb_dtype = K.dtype
+        if K.is_cuda and torch.is_autocast_enabled():
+            emb_dtype = torch.get_autocast_dtype("cuda")
+        # the posenc op is built for frame pairs; both slots get this camera
+        pe = ops.pose_embedding(torch.stack([R, R], dim=1),
+                                torch.stack([t, t], dim=1), K, None,
+                                H, W, emb_dtype)[:, frame:frame + 1]
+        zero = torch.zeros((1, 1) + tuple(pe.shape[2:]), dtype=pe.dtype,
+                           device=pe.device)
+        outs = []
+        for emb in (pe, zero):
+            if cfg.use_pos_emb:
+                emb = emb + self.pos_emb[None, None]
+            if cfg.use_ref_pose_emb:
+                emb = emb + (self.ref_pose_emb_first if frame == 0
+                             else self.ref_pose_emb_other)
+            outs.append([getattr(self, f"Conv_{i}")(emb)[:, 0]
+                         for i in range(cfg.num_resolutions)])
+        return outs[0], outs[1]
+
     def forward(self, batch: Dict[str, torch.Tensor], cond_mask: torch.Tensor,
                 pose_cache=None):
         cfg = self.cfg
@@ -205,14 +236,21 @@ class XUNet(nn.Module):
             batch, cond_mask, pose_cache=pose_cache)
 
         _emb_cache: Dict[int, torch.Tensor] = {}
+        # a pose cache that is not a plain per-level list produces the FiLM
+        # input itself (the stochastic-conditioning sampler's feature bank:
+        # fused gather + add + silu)
+        fused_emb = getattr(pose_embs, "emb", None)
 
         def emb_at(level: int) -> torch.Tensor:
             # silu((B,1,1,1,E) + (B,2,H',W',E))  (xunet.py:233,59) — the
             # silu belongs to FiLM's input; cached per level since every
             # block of a level consumes the identical tensor.
             if level not in _emb_cache:
-                e = logsnr_emb[:, None, None, None, :] + pose_embs[level]
-                _emb_cache[level] = F.silu(e)
+                if fused_emb is not None:
+                    _emb_cache[level] = fused_emb(level, logsnr_emb)
+                else:
+                    e = logsnr_emb[:, None, None, None, :] + pose_embs[level]
+                    _emb_cache[level] = F.silu(e)
             return _emb_cache[level]
 
         h = torch.stack([batch["x"], batch["z"]], dim=1)  # (B,2,H,W,3)

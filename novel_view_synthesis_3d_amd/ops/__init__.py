@@ -147,3 +147,34 @@ def pose_embedding(R, t, K, cond_mask, H: int, W: int, out_dtype):
     if _use_hip(R, "pose_embedding"):
         return _HIP_MOD.pose_embedding(R, t, K, cond_mask, H, W, out_dtype)
     return ref.pose_embedding(R, t, K, cond_mask, H, W, out_dtype)
+
+
+# ---------------------------------------------------------------------------
+# Stochastic-conditioning sampler step (ops/hip/sampler_step.hip)
+# ---------------------------------------------------------------------------
+
+stochastic_index = ref.stochastic_index  # the index rule (pure torch)
+
+
+def cond_emb_select(logsnr_emb, bank, null_feat, tgt_feat, u, step, k):
+    """silu(logsnr_emb + pose feature) for one level, the frame-0 feature of
+    the conditional half gathered from `bank` by the device-side index."""
+    if _use_hip(bank, "cond_emb_select"):
+        return _HIP_MOD.cond_emb_select(logsnr_emb, bank, null_feat,
+                                        tgt_feat, u, step, k)
+    return ref.cond_emb_select(logsnr_emb, bank, null_feat, tgt_feat, u,
+                               step, k)
+
+
+def ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma, step, u, k,
+                  bank_img, x, w: float, clip: bool,
+                  noise_scale: float = 1.0, step_scratch=None) -> None:
+    """CFG combine + ancestral step in place on z; advances `step` and
+    writes the next step's model input x from the image bank.
+    `step_scratch` is a one-element int64 work slot of the HIP kernels."""
+    if _use_hip(z, "ddpm_cfg_step"):
+        return _HIP_MOD.ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma,
+                                      step, u, k, bank_img, x, w, clip,
+                                      noise_scale, step_scratch)
+    return ref.ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma, step, u,
+                             k, bank_img, x, w, clip, noise_scale)

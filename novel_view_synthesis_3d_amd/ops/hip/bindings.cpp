@@ -47,6 +47,17 @@ torch::Tensor up2x_bwd(torch::Tensor dout);
 torch::Tensor pool2x_fwd(torch::Tensor x);
 torch::Tensor pool2x_bwd(torch::Tensor dout);
 torch::Tensor add_scale(torch::Tensor a, torch::Tensor b, double scale);
+torch::Tensor cond_emb_select(torch::Tensor lemb, torch::Tensor bank,
+                              torch::Tensor nullf, torch::Tensor tgt,
+                              torch::Tensor u, torch::Tensor step,
+                              torch::Tensor kvalid);
+void ddpm_cfg_step(torch::Tensor z, torch::Tensor out, torch::Tensor noise,
+                   torch::Tensor t_ca, torch::Tensor t_cb, torch::Tensor t_c1,
+                   torch::Tensor t_c2, torch::Tensor t_sigma,
+                   torch::Tensor step, torch::Tensor step_next,
+                   torch::Tensor u, torch::Tensor kvalid,
+                   torch::Tensor bank_img, torch::Tensor x, double w,
+                   bool clip, double noise_scale);
 
 torch::Tensor rays_posenc_py(torch::Tensor R, torch::Tensor t,
                              torch::Tensor Kinv,
@@ -82,6 +93,13 @@ TORCH_LIBRARY(nvs3d, m) {
   m.def("pool2x_fwd(Tensor x) -> Tensor");
   m.def("pool2x_bwd(Tensor dout) -> Tensor");
   m.def("add_scale(Tensor a, Tensor b, float scale) -> Tensor");
+  m.def("cond_emb_select(Tensor lemb, Tensor bank, Tensor nullf, Tensor tgt, "
+        "Tensor u, Tensor step, Tensor kvalid) -> Tensor");
+  m.def("ddpm_cfg_step(Tensor(a!) z, Tensor out, Tensor noise, Tensor t_ca, "
+        "Tensor t_cb, Tensor t_c1, Tensor t_c2, Tensor t_sigma, "
+        "Tensor(b!) step, Tensor(c!) step_next, Tensor u, Tensor kvalid, "
+        "Tensor bank_img, Tensor(d!) x, float w, bool clip, "
+        "float noise_scale) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(nvs3d, CUDA, m) {
@@ -103,4 +121,6 @@ TORCH_LIBRARY_IMPL(nvs3d, CUDA, m) {
   m.impl("pool2x_fwd", pool2x_fwd);
   m.impl("pool2x_bwd", pool2x_bwd);
   m.impl("add_scale", add_scale);
+  m.impl("cond_emb_select", cond_emb_select);
+  m.impl("ddpm_cfg_step", ddpm_cfg_step);
 }

@@ -9,8 +9,10 @@
 // Layout: x is (B, F*H*W = R rows, C) contiguous NHWC-with-frames. Thread
 // mapping: each thread owns a FIXED channel span [c0, c0+V) (V | Cg so the
 // span stays inside one group) and strides over rows — fully coalesced
-// 16-byte loads, per-thread register gamma/beta, one LDS atomic per thread
-// per reduction. Grid = B * P row-chunks so the launch fills 256 CUs
+// 16-byte loads, per-thread register gamma/beta. The forward reduces its
+// per-thread partials through LDS in a fixed order (bitwise reproducible
+// from call to call); the backward uses one LDS atomic per thread per
+// reduction. Grid = B * P row-chunks so the launch fills 256 CUs
 // (one block per (b, chunk); stats finalized per-block by re-reducing the
 // tiny (B, G, P) partial buffer).
 //
@@ -31,6 +33,7 @@
 namespace {
 
 constexpr int MAX_GROUPS = 32;
+constexpr int MAX_THREADS = 1024;  // pick_block's cap on the block size
 
 // Counter-based dropout mask: PCG hash of (element index, seed). The
 // backward REGENERATES the mask from the same seed — no mask tensor.
@@ -66,18 +69,18 @@ template <typename T, int V>
 __global__ void gn_fwd_partials(const T* __restrict__ x,
                                 float* __restrict__ partials,
                                 GnShape s) {
-  __shared__ float lsum[MAX_GROUPS], lsumsq[MAX_GROUPS];
+  // per-thread partials, reduced in a FIXED order below: the forward is
+  // bitwise reproducible from call to call (float atomics are not, and the
+  // sampler amplifies a last-bit difference in the statistics into O(1))
+  __shared__ float ps1[MAX_THREADS], ps2[MAX_THREADS];
   const int b = blockIdx.x / s.P;
   const int chunk = blockIdx.x % s.P;
   const int tid = threadIdx.x;
-  if (tid < s.G) { lsum[tid] = 0.f; lsumsq[tid] = 0.f; }
-  __syncthreads();
 
   const int rowsPerIter = s.T / s.rowThreads;
   const int rt = tid % s.rowThreads;
   const int ri = tid / s.rowThreads;
   const int c0 = rt * V;
-  const int g = c0 / s.Cg;
 
   const int rc = (s.R + s.P - 1) / s.P;
   const int r0 = chunk * rc;
@@ -94,13 +97,21 @@ __global__ void gn_fwd_partials(const T* __restrict__ x,
       s2 += xv * xv;
     }
   }
-  atomicAdd(&lsum[g], s1);
-  atomicAdd(&lsumsq[g], s2);
+  ps1[tid] = s1;
+  ps2[tid] = s2;
   __syncthreads();
   if (tid < s.G) {
+    // group `tid` is covered by tpg consecutive row threads in each of the
+    // rowsPerIter row slots (V divides Cg, T = rowsPerIter * rowThreads)
+    const int tpg = s.Cg / V;
+    float a1 = 0.f, a2 = 0.f;
+    for (int i = 0; i < rowsPerIter; ++i) {
+      const int t0 = i * s.rowThreads + tid * tpg;
+      for (int j = 0; j < tpg; ++j) { a1 += ps1[t0 + j]; a2 += ps2[t0 + j]; }
+    }
     float* dst = partials + (((size_t)b * s.G + tid) * s.P + chunk) * 2;
-    dst[0] = lsum[tid];
-    dst[1] = lsumsq[tid];
+    dst[0] = a1;
+    dst[1] = a2;
   }
 }
 

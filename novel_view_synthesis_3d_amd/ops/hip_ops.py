@@ -558,3 +558,33 @@ def residual_scale_add(h, h_in):
         return _AddScale.apply(h, h_in, 1.0 / math.sqrt(2.0))
     from novel_view_synthesis_3d_amd.ops import reference as _ref
     return _ref.residual_scale_add(h, h_in)
+
+
+# ---------------------------------------------------------------------------
+# Stochastic-conditioning sampler step (sampler_step.hip); inference only
+# ---------------------------------------------------------------------------
+
+HAS |= {"cond_emb_select", "ddpm_cfg_step"}
+
+
+def cond_emb_select(logsnr_emb, bank, null_feat, tgt_feat, u, step, k):
+    dt = bank.dtype
+    with torch.no_grad():
+        return _OPS.cond_emb_select(
+            logsnr_emb.to(dt).contiguous(), bank, null_feat.to(dt).contiguous(),
+            tgt_feat.to(dt).contiguous(), u, step, k)
+
+
+def ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma, step, u, k,
+                  bank_img, x, w, clip, noise_scale=1.0,
+                  step_scratch=None) -> None:
+    """`step_scratch`: one-element int64 slot the step kernel writes the
+    advanced counter to (its other blocks may still be reading the live
+    one); the gather kernel publishes it. A caller that steps repeatedly
+    (or under graph capture) keeps one next to `step`."""
+    if step_scratch is None:
+        step_scratch = torch.empty_like(step)
+    with torch.no_grad():
+        _OPS.ddpm_cfg_step(z, out.contiguous(), noise, c_a, c_b, c1, c2,
+                           sigma, step, step_scratch, u, k, bank_img, x,
+                           float(w), bool(clip), float(noise_scale))

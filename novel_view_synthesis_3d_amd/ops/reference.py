@@ -180,3 +180,73 @@ def pose_embedding(R: torch.Tensor, t: torch.Tensor, K: torch.Tensor,
     if cond_mask is not None:
         pe = pe * cond_mask.to(pe.dtype).reshape(-1, 1, 1, 1, 1)
     return pe.to(out_dtype)
+
+
+# ---------------------------------------------------------------------------
+# Stochastic-conditioning sampler step (oracles for ops/hip/sampler_step.hip)
+# ---------------------------------------------------------------------------
+
+def stochastic_index(u: torch.Tensor, k) -> torch.Tensor:
+    """The index rule: idx = min(floor(u * k), k - 1), evaluated in fp32.
+
+    u: uniforms in [0,1) of any shape; k: number of valid bank entries (int
+    or one-element tensor). Returns int64 indices of u's shape."""
+    kf = torch.as_tensor(k, device=u.device).reshape(()).to(torch.float32)
+    idx = torch.floor(u.to(torch.float32) * kf)
+    idx = torch.minimum(idx, kf - 1.0).clamp_(min=0.0)
+    return idx.to(torch.long)
+
+
+def cond_emb_select(logsnr_emb: torch.Tensor, bank: torch.Tensor,
+                    null_feat: torch.Tensor, tgt_feat: torch.Tensor,
+                    u: torch.Tensor, step: torch.Tensor,
+                    k: torch.Tensor) -> torch.Tensor:
+    """Per-level FiLM input with the conditioning view picked from a bank.
+
+    logsnr_emb (2B,E); bank (Kcap,B,H',W',E); null_feat (B|1,H',W',E);
+    tgt_feat (2B,H',W',E); u (S,B) uniforms; step, k one-element int64.
+    Returns (2B,2,H',W',E) = silu(logsnr_emb[r] + feat) in bank.dtype, where
+    feat is bank[idx[b], b] (frame 0, rows < B), null_feat (frame 0, rows
+    >= B) or tgt_feat (frame 1). fp32 arithmetic, one rounding."""
+    B = bank.shape[1]
+    idx = stochastic_index(u.index_select(0, step.reshape(1))[0], k)  # (B,)
+    rows = torch.arange(B, device=bank.device)
+    src = bank[idx, rows].to(torch.float32)                 # (B,H',W',E)
+    null = null_feat.to(torch.float32).expand(B, *bank.shape[2:])
+    frame0 = torch.cat([src, null], dim=0)
+    feat = torch.stack([frame0, tgt_feat.to(torch.float32)], dim=1)
+    e = logsnr_emb.to(torch.float32)[:, None, None, None, :] + feat
+    return F.silu(e).to(bank.dtype)
+
+
+def ddpm_cfg_step(z: torch.Tensor, out: torch.Tensor, noise: torch.Tensor,
+                  c_a: torch.Tensor, c_b: torch.Tensor, c1: torch.Tensor,
+                  c2: torch.Tensor, sigma: torch.Tensor, step: torch.Tensor,
+                  u: torch.Tensor, k: torch.Tensor, bank_img: torch.Tensor,
+                  x: torch.Tensor, w: float, clip: bool,
+                  noise_scale: float = 1.0) -> None:
+    """One post-network ancestral step, in place on z, step and x.
+
+    eps = (1+w) out[:B] - w out[B:];  x0 = c_a z - c_b eps (clamped to
+    [-1,1] if clip);  z <- c1 x0 + c2 z + noise_scale sigma noise, with the
+    coefficients taken from the (S,) tables at `step`. Then step += 1 and,
+    while steps remain, x (2B,...) <- bank_img[idx_next[b], b] for both CFG
+    halves under the index rule at the advanced step."""
+    B = z.shape[0]
+    S = u.shape[0]
+    s = step.reshape(1)
+    o = out.to(torch.float32)
+    eps = (1.0 + w) * o[:B] - w * o[B:]
+    x0 = c_a.index_select(0, s) * z - c_b.index_select(0, s) * eps
+    if clip:
+        x0 = x0.clamp(-1.0, 1.0)
+    mean = c1.index_select(0, s) * x0 + c2.index_select(0, s) * z
+    z.copy_(mean + (noise_scale * sigma.index_select(0, s)) * noise)
+    step.add_(1)
+    # no data-dependent host branch: past the last step the clamped row is
+    # gathered and then discarded by the where()
+    s1 = step.reshape(1).clamp(max=S - 1)
+    idx = stochastic_index(u.index_select(0, s1)[0], k)
+    nxt = bank_img[idx, torch.arange(B, device=z.device)]
+    live = (step.reshape(()) < S)
+    x.copy_(torch.where(live, torch.cat([nxt, nxt], dim=0), x))
