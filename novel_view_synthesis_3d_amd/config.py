@@ -92,6 +92,11 @@ class TrainConfig:
     data: str = "auto"                 # "auto" | "synthetic" | "srn"
     num_workers: int = 4
     resume: Optional[str] = None       # checkpoint path to resume from
+    # Training recipe (3DiM / DDPM practice; absent from the reference):
+    max_grad_norm: Optional[float] = None  # clip by global grad norm
+    ema_decay: Optional[float] = None  # EMA of the weights (what sampling uses)
+    ema_warmup: bool = True            # decay_t = min(ema_decay, (1+t)/(10+t))
+    lr_warmup_steps: int = 0           # linear LR warmup over this many steps
 
 
 @dataclass

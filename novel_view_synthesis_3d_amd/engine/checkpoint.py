@@ -209,11 +209,57 @@ def find_latest(ckpt_dir: str, prefix: str = "model") -> Optional[str]:
     return os.path.join(ckpt_dir, sorted(cands)[-1])
 
 
+def has_ema(payload: dict) -> bool:
+    """True when the checkpoint's optimizer state carries an EMA copy."""
+    opt = payload.get("optimizer") or {}
+    state = opt.get("state") or {}
+    return bool(state) and all("ema" in st for st in state.values())
+
+
+def ema_state_dict(payload: dict, model: torch.nn.Module) -> Dict[str, torch.Tensor]:
+    """Name-keyed state dict with the parameters replaced by their EMA.
+
+    The EMA is stored once, in the optimizer state
+    (payload["optimizer"]["state"][i]["ema"], FusedAdam's layout); i follows
+    the optimizer's param order, which is model.parameters() order as the
+    Trainer builds it. Buffers and other non-parameter entries come from
+    payload["model"]."""
+    if not has_ema(payload):
+        raise KeyError("checkpoint carries no EMA weights (it was trained "
+                       "without ema_decay)")
+    state = payload["optimizer"]["state"]
+    named = list(model.named_parameters())
+    if len(state) != len(named):
+        raise ValueError(f"optimizer state has {len(state)} entries, the "
+                         f"model has {len(named)} parameters")
+    out = dict(payload["model"])
+    for i, (name, p) in enumerate(named):
+        if i not in state:
+            raise KeyError(f"optimizer state has no entry {i} ({name})")
+        ema = state[i]["ema"]
+        if tuple(ema.shape) != tuple(p.shape) or name not in out:
+            raise ValueError(
+                f"EMA entry {i} has shape {tuple(ema.shape)}, parameter "
+                f"{name} has {tuple(p.shape)}: optimizer param order does "
+                f"not match this model")
+        out[name] = ema
+    return out
+
+
 def load_checkpoint(path: str, model: torch.nn.Module,
                     optimizer: Optional[torch.optim.Optimizer] = None,
-                    map_location="cpu") -> int:
-    payload = torch.load(path, map_location=map_location, weights_only=False)
-    model.load_state_dict(payload["model"])
+                    map_location="cpu", use_ema: bool = False,
+                    payload: Optional[dict] = None) -> int:
+    """Load a native checkpoint. `use_ema` loads the EMA copy of the weights
+    into the model (raises if the checkpoint has none). A `payload` already
+    read from `path` is used as is instead of reading the file again."""
+    if payload is None:
+        payload = torch.load(path, map_location=map_location,
+                             weights_only=False)
+    if use_ema:
+        model.load_state_dict(ema_state_dict(payload, model))
+    else:
+        model.load_state_dict(payload["model"])
     if optimizer is not None and payload.get("optimizer") is not None:
         optimizer.load_state_dict(payload["optimizer"])
     return int(payload["step"])

@@ -20,6 +20,18 @@ torch::Tensor rays_posenc(torch::Tensor R, torch::Tensor t, torch::Tensor Kinv,
 void fused_adam(torch::Tensor ptrs, torch::Tensor chunk_tensor,
                 torch::Tensor chunk_off, torch::Tensor numels,
                 double lr, double b1, double b2, double eps, int64_t step);
+void fused_adam_recipe(torch::Tensor ptrs,
+                       c10::optional<torch::Tensor> ema_ptrs,
+                       torch::Tensor chunk_tensor, torch::Tensor chunk_off,
+                       torch::Tensor numels,
+                       c10::optional<torch::Tensor> ctrl,
+                       double lr, double b1, double b2, double eps,
+                       int64_t step, double ema_decay);
+void grad_sqnorm(torch::Tensor ptrs, torch::Tensor chunk_tensor,
+                 torch::Tensor chunk_off, torch::Tensor numels,
+                 torch::Tensor partials, int64_t partial_off);
+void grad_norm_finalize(torch::Tensor partials, torch::Tensor ctrl,
+                        double max_norm);
 torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w,
                           c10::optional<torch::Tensor> bias,
                           c10::optional<torch::Tensor> residual,
@@ -78,6 +90,13 @@ TORCH_LIBRARY(nvs3d, m) {
   m.def("fused_adam(Tensor ptrs, Tensor chunk_tensor, Tensor chunk_off, "
         "Tensor numels, float lr, float b1, float b2, float eps, "
         "int step) -> ()");
+  m.def("fused_adam_recipe(Tensor ptrs, Tensor? ema_ptrs, Tensor chunk_tensor, "
+        "Tensor chunk_off, Tensor numels, Tensor? ctrl, float lr, float b1, "
+        "float b2, float eps, int step, float ema_decay) -> ()");
+  m.def("grad_sqnorm(Tensor ptrs, Tensor chunk_tensor, Tensor chunk_off, "
+        "Tensor numels, Tensor(a!) partials, int partial_off) -> ()");
+  m.def("grad_norm_finalize(Tensor partials, Tensor(a!) ctrl, "
+        "float max_norm) -> ()");
   m.def("conv3x3_fwd(Tensor x, Tensor w, Tensor? bias, Tensor? residual, float out_scale) -> Tensor");
   m.def("conv3x3_wgrad(Tensor x, Tensor dy, bool with_bias) -> Tensor[]");
   m.def("linear_wgrad(Tensor dy, Tensor x, bool with_bias) -> Tensor[]");
@@ -107,6 +126,9 @@ TORCH_LIBRARY_IMPL(nvs3d, CUDA, m) {
   m.impl("gn_bwd", gn_bwd);
   m.impl("rays_posenc", rays_posenc_py);
   m.impl("fused_adam", fused_adam);
+  m.impl("fused_adam_recipe", fused_adam_recipe);
+  m.impl("grad_sqnorm", grad_sqnorm);
+  m.impl("grad_norm_finalize", grad_norm_finalize);
   m.impl("conv3x3_fwd", conv3x3_fwd);
   m.impl("conv3x3_wgrad", conv3x3_wgrad);
   m.impl("linear_wgrad", linear_wgrad);

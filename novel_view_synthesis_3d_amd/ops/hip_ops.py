@@ -128,33 +128,90 @@ CHUNK = 1 << 16
 
 
 class AdamPlan:
-    """Cached pointer table + chunk map for a fixed set of (p,g,m,v)."""
+    """Cached pointer table + chunk map for a fixed set of (p,g,m,v), plus
+    an optional (n,) table of EMA pointers. p, m, v and ema come straight
+    from the allocator; g may be a view into a flat data-parallel bucket at
+    any element offset (4-byte aligned) — the kernels pick the scalar loop
+    per chunk in that case.
 
-    def __init__(self, tuples, device):
-        self.key = [ (p.data_ptr(), g.data_ptr()) for p, g, _, _ in tuples ]
+    The plan stores raw device addresses, not references: the caller (the
+    optimizer state, normally) must keep every tensor alive while the plan
+    is in use."""
+
+    def __init__(self, tuples, device, emas=None):
+        self.key = self._key(tuples, emas)
         ptrs, numels = [], []
         chunk_tensor, chunk_off = [], []
         for i, (p, g, m, v) in enumerate(tuples):
             assert p.dtype == torch.float32 and p.is_contiguous()
+            for t in (g, m, v) + (() if emas is None else (emas[i],)):
+                assert (t.dtype == torch.float32 and t.is_contiguous()
+                        and t.numel() == p.numel() and t.device == p.device)
             ptrs += [p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()]
             numels.append(p.numel())
             for off in range(0, p.numel(), CHUNK):
                 chunk_tensor.append(i)
                 chunk_off.append(off)
+        self.nchunks = len(chunk_tensor)
         self.ptrs = torch.tensor(ptrs, dtype=torch.uint64).to(device)
         self.numels = torch.tensor(numels, dtype=torch.int64).to(device)
         self.chunk_tensor = torch.tensor(chunk_tensor,
                                          dtype=torch.int32).to(device)
         self.chunk_off = torch.tensor(chunk_off, dtype=torch.int64).to(device)
+        self.ema_ptrs = None
+        if emas is not None:
+            assert len(emas) == len(tuples)
+            self.ema_ptrs = torch.tensor([e.data_ptr() for e in emas],
+                                         dtype=torch.uint64).to(device)
 
-    def matches(self, tuples) -> bool:
-        return self.key == [(p.data_ptr(), g.data_ptr())
-                            for p, g, _, _ in tuples]
+    @staticmethod
+    def _key(tuples, emas):
+        key = [(p.data_ptr(), g.data_ptr()) for p, g, _, _ in tuples]
+        if emas is not None:
+            key.append(tuple(e.data_ptr() for e in emas))
+        return key
+
+    def matches(self, tuples, emas=None) -> bool:
+        return self.key == self._key(tuples, emas)
 
 
 def fused_adam_step(plan: AdamPlan, lr, b1, b2, eps, step: int) -> None:
     _OPS.fused_adam(plan.ptrs, plan.chunk_tensor, plan.chunk_off, plan.numels,
                     lr, b1, b2, eps, step)
+
+
+def grad_norm_ctrl(device) -> torch.Tensor:
+    """Device control buffer [norm, scale, skip, skipped_steps] (fp32)."""
+    return torch.zeros(4, dtype=torch.float32, device=device)
+
+
+def fused_grad_norm(plans, partials: torch.Tensor, ctrl: torch.Tensor,
+                    max_norm: float) -> None:
+    """Global L2 norm of every plan's gradients -> ctrl, without a host
+    sync: one partial per 64K chunk in fixed order, then one finalize block
+    (scale = min(1, max_norm / (norm + 1e-6)), skip = norm not finite)."""
+    assert partials.numel() == sum(pl.nchunks for pl in plans)
+    off = 0
+    for pl in plans:
+        _OPS.grad_sqnorm(pl.ptrs, pl.chunk_tensor, pl.chunk_off, pl.numels,
+                         partials, off)
+        off += pl.nchunks
+    _OPS.grad_norm_finalize(partials, ctrl, max_norm)
+
+
+def fused_adam_recipe_step(plan: AdamPlan, lr, b1, b2, eps, step: int,
+                           ctrl: Optional[torch.Tensor] = None,
+                           ema_decay: Optional[float] = None) -> None:
+    """Adam update with the clip factor / skip flag read from `ctrl` (when
+    given) and the EMA folded into the same pass (when `ema_decay` is given;
+    the plan must carry the EMA pointers)."""
+    ema_ptrs = None
+    if ema_decay is not None:
+        assert plan.ema_ptrs is not None, "plan was built without EMA tensors"
+        ema_ptrs = plan.ema_ptrs
+    _OPS.fused_adam_recipe(plan.ptrs, ema_ptrs, plan.chunk_tensor,
+                           plan.chunk_off, plan.numels, ctrl, lr, b1, b2, eps,
+                           step, 0.0 if ema_decay is None else ema_decay)
 
 
 # ---------------------------------------------------------------------------

@@ -9,6 +9,9 @@ Multi-view (stochastic conditioning, 3DiM §2.2): N views of one object from
 its first observation, each step conditioned on a random earlier view.
 
     python sample.py --checkpoint ... --folder cars_train_val --views 8
+
+Checkpoints trained with --ema-decay carry an EMA copy of the weights; it is
+used by default (--no-ema samples from the raw weights).
 """
 
 import argparse
@@ -111,12 +114,16 @@ def main() -> None:
     ap.add_argument("--max-bank", type=int, default=None,
                     help="with --views: keep only the M most recent views "
                          "in the conditioning bank")
+    ap.add_argument("--ema", default=None,
+                    action=argparse.BooleanOptionalAction,
+                    help="sample from the EMA weights (default: use them "
+                         "when the checkpoint carries them)")
     args = ap.parse_args()
 
     device = "cuda" if torch.cuda.is_available() else "cpu"
     # the checkpoint's extra payload records the model config and sidelength;
     # CLI flags override, and are required only for configless checkpoints
-    payload = torch.load(args.checkpoint, map_location="cpu",
+    payload = torch.load(args.checkpoint, map_location=device,
                          weights_only=False)
     extra = payload.get("extra", {}) if isinstance(payload, dict) else {}
     if args.model is not None:
@@ -129,7 +136,11 @@ def main() -> None:
                   else int(extra.get("img_sidelength", 64)))
     args.sidelength = sidelength
     model = XUNet(model_cfg, sidelength).to(device)
-    ckpt.load_checkpoint(args.checkpoint, model, map_location=device)
+    use_ema = ckpt.has_ema(payload) if args.ema is None else args.ema
+    ckpt.load_checkpoint(args.checkpoint, model, use_ema=use_ema,
+                         payload=payload)
+    print(f"loaded {'EMA' if use_ema else 'raw'} weights from "
+          f"{args.checkpoint}")
     model.eval()
 
     if args.views is not None:

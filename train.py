@@ -37,6 +37,17 @@ def main() -> None:
     ap.add_argument("--resume", default=None,
                     help="checkpoint path, or 'auto'")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip gradients to this global L2 norm; steps with "
+                         "a non-finite norm are skipped")
+    ap.add_argument("--ema-decay", type=float, default=None,
+                    help="keep an EMA of the weights (e.g. 0.9999); "
+                         "sample.py uses it when present")
+    ap.add_argument("--no-ema-warmup", action="store_true",
+                    help="use --ema-decay from step 1 instead of "
+                         "min(decay, (1+t)/(10+t))")
+    ap.add_argument("--lr-warmup-steps", type=int, default=None,
+                    help="linear learning-rate warmup over N steps")
     ap.add_argument("--profile", action="store_true",
                     help="torch.profiler trace of 5 steps, then exit")
     args = ap.parse_args()
@@ -52,6 +63,15 @@ def main() -> None:
     train_cfg.data = args.data
     train_cfg.resume = args.resume
     train_cfg.seed = args.seed
+    # recipe flags override the YAML config only when given
+    if args.max_grad_norm is not None:
+        train_cfg.max_grad_norm = args.max_grad_norm
+    if args.ema_decay is not None:
+        train_cfg.ema_decay = args.ema_decay
+    if args.no_ema_warmup:
+        train_cfg.ema_warmup = False
+    if args.lr_warmup_steps is not None:
+        train_cfg.lr_warmup_steps = args.lr_warmup_steps
 
     trainer = Trainer(args.folder,
                       train_batch_size=args.batch_size,
