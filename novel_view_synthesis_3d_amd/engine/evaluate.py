@@ -1,0 +1,215 @@
+"""Test-set evaluation: PSNR / SSIM of generated views (SRN single-view
+protocol, as used by PixelNeRF and 3DiM).
+
+For every object instance under a dataset root one observation is the input
+view and every other view (or an evenly spaced subset) is generated with
+`StochasticConditioningSampler.sample_views` and compared with the ground
+truth. Metrics come from `ops.image_metrics` — on the GPU one fused launch
+pair per batch of objects, results left on the device until the batch's one
+host transfer.
+"""
+
+from __future__ import annotations
+
+import math
+import os
+from glob import glob
+from typing import Dict, List, Optional
+
+import numpy as np
+import torch
+
+from novel_view_synthesis_3d_amd import ops
+from novel_view_synthesis_3d_amd.data.srn import SceneInstanceDataset
+from novel_view_synthesis_3d_amd.diffusion.sampler import (
+    StochasticConditioningSampler,
+)
+
+MODES = ("autoregressive", "independent")
+
+
+def _finite_or_none(x: float) -> Optional[float]:
+    return float(x) if math.isfinite(x) else None
+
+
+def to_serialisable(result: Dict) -> Dict:
+    """`Evaluator.evaluate`'s dict as plain JSON data: image tensors are
+    dropped and a non-finite PSNR (identical images) becomes None."""
+    out = {k: v for k, v in result.items() if k not in ("images", "targets")}
+    out["psnr"] = _finite_or_none(out["psnr"])
+    out["per_instance"] = [dict(e, psnr=_finite_or_none(e["psnr"]))
+                           for e in out["per_instance"]]
+    return out
+
+
+def _save_png(img_u8: np.ndarray, path: str) -> None:
+    try:
+        from PIL import Image
+        Image.fromarray(img_u8).save(path)
+    except ImportError:
+        np.save(path.replace(".png", ".npy"), img_u8)
+
+
+class Evaluator:
+    """mode="autoregressive": every denoising step of a view is conditioned
+    on a view drawn from the input plus the views generated so far (3DiM
+    stochastic conditioning); mode="independent": always on the input view.
+    `quantize` evaluates the 8-bit values sample.py writes to PNG."""
+
+    def __init__(self, model, num_steps: int, guidance_weight: float = 3.0,
+                 mode: str = "autoregressive",
+                 max_bank: Optional[int] = None, use_graph: bool = False,
+                 batch_objects: int = 1, seed: int = 0,
+                 quantize: bool = False):
+        if mode not in MODES:
+            raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+        if batch_objects < 1:
+            raise ValueError("batch_objects must be >= 1")
+        self.model = model
+        self.num_steps = int(num_steps)
+        self.guidance_weight = float(guidance_weight)
+        self.mode = mode
+        self.max_bank = max_bank
+        self.use_graph = bool(use_graph)
+        self.batch_objects = int(batch_objects)
+        self.seed = int(seed)
+        self.quantize = bool(quantize)
+
+    # -----------------------------------------------------------------
+    @staticmethod
+    def _instances(root: str, sidelength: int, input_view: int,
+                   num_targets: Optional[int], max_instances: int) -> List:
+        """[(name, dataset, target view indices)] in sorted order."""
+        dirs = sorted(glob(os.path.join(root, "*/")))
+        if not dirs:
+            raise FileNotFoundError(f"no instances under {root!r}")
+        if max_instances != -1:
+            dirs = dirs[:max_instances]
+        out = []
+        for i, d in enumerate(dirs):
+            name = os.path.basename(os.path.normpath(d))
+            inst = SceneInstanceDataset(i, d, img_sidelength=sidelength)
+            n = len(inst)
+            if input_view < 0 or input_view >= n or n < 2:
+                raise ValueError(
+                    f"instance {name!r} has {n} views: too few for "
+                    f"--input-view {input_view} plus one target view")
+            others = [j for j in range(n) if j != input_view]
+            if num_targets is not None:
+                k = min(int(num_targets), len(others))
+                if k < 1:
+                    raise ValueError("--num-targets must be >= 1")
+                idcs = np.linspace(0, stop=len(others), num=k,
+                                   endpoint=False, dtype=int)
+                others = [others[j] for j in idcs]
+            out.append((name, inst, others))
+        return out
+
+    def _batches(self, instances: List) -> List[List]:
+        """Consecutive instances with equal target counts, batch_objects at
+        most per batch."""
+        batches, cur = [], []
+        for item in instances:
+            if cur and (len(cur) == self.batch_objects
+                        or len(cur[0][2]) != len(item[2])):
+                batches.append(cur)
+                cur = []
+            cur.append(item)
+        if cur:
+            batches.append(cur)
+        return batches
+
+    # -----------------------------------------------------------------
+    @torch.no_grad()
+    def evaluate(self, root: str, sidelength: int, input_view: int = 64,
+                 num_targets: Optional[int] = None, max_instances: int = -1,
+                 save_images_dir: Optional[str] = None,
+                 return_images: bool = False) -> Dict:
+        model = self.model
+        was_training = model.training
+        model.eval()
+        try:
+            return self._evaluate(root, sidelength, input_view, num_targets,
+                                  max_instances, save_images_dir,
+                                  return_images)
+        finally:
+            model.train(was_training)
+
+    def _evaluate(self, root, sidelength, input_view, num_targets,
+                  max_instances, save_images_dir, return_images) -> Dict:
+        device = next(self.model.parameters()).device
+        instances = self._instances(root, sidelength, input_view,
+                                    num_targets, max_instances)
+        sampler = StochasticConditioningSampler(self.model,
+                                                max_bank=self.max_bank)
+        per_instance, images, targets = [], [], []
+        view_psnr, view_ssim = [], []
+        for bi, batch in enumerate(self._batches(instances)):
+            inp = [inst[input_view] for _, inst, _ in batch]
+            tgt = [[inst[j] for j in views] for _, inst, views in batch]
+            B, N = len(batch), len(tgt[0])
+
+            def stack_in(key):
+                return torch.stack([o[key] for o in inp]).to(device)
+
+            def stack_tgt(key):  # (N,B,...)
+                return torch.stack([torch.stack([tgt[b][n][key]
+                                                 for b in range(B)])
+                                    for n in range(N)]).to(device)
+
+            gt = stack_tgt("x")
+            torch.manual_seed(self.seed + bi)
+            out = sampler.sample_views(
+                stack_in("x"), stack_in("R1"), stack_in("t1"), stack_in("K"),
+                stack_tgt("R1"), stack_tgt("t1"), num_steps=self.num_steps,
+                guidance_weight=self.guidance_weight, clip_denoised=True,
+                seed=self.seed + bi,
+                use_graph=self.use_graph and device.type == "cuda",
+                stochastic=self.mode == "autoregressive")
+            out = out.clamp(-1.0, 1.0)
+            H, W = out.shape[2:4]
+            psnr, ssim = ops.image_metrics(out.reshape(N * B, H, W, 3),
+                                           gt.reshape(N * B, H, W, 3),
+                                           quantize=self.quantize)
+            # the batch's one host transfer: (2,N,B) in double
+            m = torch.stack([psnr, ssim]).double().reshape(2, N, B).cpu()
+            for b, (name, _, views) in enumerate(batch):
+                view_psnr.append(m[0, :, b])
+                view_ssim.append(m[1, :, b])
+                per_instance.append({"name": name,
+                                     "psnr": float(m[0, :, b].mean()),
+                                     "ssim": float(m[1, :, b].mean()),
+                                     "n_views": N})
+                if return_images:  # instance-major, like view_psnr
+                    images.append(out[:, b].cpu())
+                    targets.append(gt[:, b].cpu())
+                if save_images_dir is not None:
+                    d = os.path.join(save_images_dir, name)
+                    os.makedirs(d, exist_ok=True)
+                    u8 = ((out[:, b] * 0.5 + 0.5) * 255).to(
+                        torch.uint8).cpu().numpy()
+                    for n, v in enumerate(views):
+                        _save_png(u8[n], os.path.join(d, f"{v:06d}.png"))
+
+        all_psnr, all_ssim = torch.cat(view_psnr), torch.cat(view_ssim)
+        result = {
+            "psnr": float(all_psnr.mean()),
+            "ssim": float(all_ssim.mean()),
+            "n_instances": len(per_instance),
+            "n_views": int(all_psnr.numel()),
+            "per_instance": per_instance,
+            "settings": {
+                "root": root, "sidelength": int(sidelength),
+                "input_view": int(input_view), "num_targets": num_targets,
+                "max_instances": int(max_instances),
+                "num_steps": self.num_steps,
+                "guidance_weight": self.guidance_weight, "mode": self.mode,
+                "max_bank": self.max_bank, "use_graph": self.use_graph,
+                "batch_objects": self.batch_objects, "seed": self.seed,
+                "quantize": self.quantize,
+            },
+        }
+        if return_images:
+            result["images"] = torch.cat(images)      # (n_views,H,W,3)
+            result["targets"] = torch.cat(targets)
+        return result

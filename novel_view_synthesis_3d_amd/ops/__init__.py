@@ -178,3 +178,20 @@ def ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma, step, u, k,
                                       noise_scale, step_scratch)
     return ref.ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma, step, u,
                              k, bank_img, x, w, clip, noise_scale)
+
+
+# ---------------------------------------------------------------------------
+# Image quality metrics (ops/hip/image_metrics.hip)
+# ---------------------------------------------------------------------------
+
+def image_metrics(pred, target, quantize: bool = False):
+    """PSNR (dB) and SSIM of (N,H,W,3) image pairs in [-1,1]; two (N,)
+    tensors on the inputs' device (definition: ref.image_metrics). fp32 and
+    bf16 inputs on the GPU take the fused kernel: fp32 results, no host
+    sync. H or W below the 11-pixel SSIM window raises ValueError."""
+    ref.check_image_pair(pred, target)
+    pred, target = pred.contiguous(), target.contiguous()
+    if (_use_hip(pred, "image_metrics")
+            and pred.dtype in (torch.float32, torch.bfloat16)):
+        return _HIP_MOD.image_metrics(pred, target, quantize)
+    return ref.image_metrics(pred, target, quantize)

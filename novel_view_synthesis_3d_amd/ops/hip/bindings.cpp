@@ -70,6 +70,10 @@ void ddpm_cfg_step(torch::Tensor z, torch::Tensor out, torch::Tensor noise,
                    torch::Tensor u, torch::Tensor kvalid,
                    torch::Tensor bank_img, torch::Tensor x, double w,
                    bool clip, double noise_scale);
+std::vector<torch::Tensor> image_metrics(torch::Tensor pred,
+                                         torch::Tensor target,
+                                         bool quantize);
+int64_t image_metrics_tile();
 
 torch::Tensor rays_posenc_py(torch::Tensor R, torch::Tensor t,
                              torch::Tensor Kinv,
@@ -119,6 +123,9 @@ TORCH_LIBRARY(nvs3d, m) {
         "Tensor(b!) step, Tensor(c!) step_next, Tensor u, Tensor kvalid, "
         "Tensor bank_img, Tensor(d!) x, float w, bool clip, "
         "float noise_scale) -> ()");
+  m.def("image_metrics(Tensor pred, Tensor target, bool quantize) "
+        "-> Tensor[]");
+  m.def("image_metrics_tile() -> int", image_metrics_tile);
 }
 
 TORCH_LIBRARY_IMPL(nvs3d, CUDA, m) {
@@ -145,4 +152,5 @@ TORCH_LIBRARY_IMPL(nvs3d, CUDA, m) {
   m.impl("add_scale", add_scale);
   m.impl("cond_emb_select", cond_emb_select);
   m.impl("ddpm_cfg_step", ddpm_cfg_step);
+  m.impl("image_metrics", image_metrics);
 }

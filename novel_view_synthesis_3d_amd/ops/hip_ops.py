@@ -645,3 +645,22 @@ def ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma, step, u, k,
         _OPS.ddpm_cfg_step(z, out.contiguous(), noise, c_a, c_b, c1, c2,
                            sigma, step, step_scratch, u, k, bank_img, x,
                            float(w), bool(clip), float(noise_scale))
+
+
+# ---------------------------------------------------------------------------
+# Fused PSNR + SSIM (image_metrics.hip); inference only
+# ---------------------------------------------------------------------------
+
+HAS |= {"image_metrics"}
+
+# valid window positions per side of one block's tile (tests size their
+# one-tile and one-tile-plus-a-strip cases from it)
+IMAGE_METRICS_TILE = int(_OPS.image_metrics_tile())
+
+
+def image_metrics(pred, target, quantize=False):
+    """(psnr, ssim), each (N,) fp32 on the device; contiguous (N,H,W,3)
+    fp32/bf16 inputs. One metric launch + one finalize launch, no sync."""
+    with torch.no_grad():
+        psnr, ssim = _OPS.image_metrics(pred, target, bool(quantize))
+    return psnr, ssim

@@ -250,3 +250,82 @@ def ddpm_cfg_step(z: torch.Tensor, out: torch.Tensor, noise: torch.Tensor,
     nxt = bank_img[idx, torch.arange(B, device=z.device)]
     live = (step.reshape(()) < S)
     x.copy_(torch.where(live, torch.cat([nxt, nxt], dim=0), x))
+
+
+# ---------------------------------------------------------------------------
+# Image quality metrics (oracle for ops/hip/image_metrics.hip)
+# ---------------------------------------------------------------------------
+
+SSIM_WINDOW = 11
+SSIM_SIGMA = 1.5
+SSIM_C1 = 0.01 ** 2
+SSIM_C2 = 0.03 ** 2
+
+
+def ssim_window(dtype=torch.float64, device=None) -> torch.Tensor:
+    """The 11-tap Gaussian (sigma 1.5), normalised to sum 1 in fp64."""
+    x = torch.arange(SSIM_WINDOW, dtype=torch.float64) - (SSIM_WINDOW - 1) / 2
+    g = torch.exp(-(x * x) / (2.0 * SSIM_SIGMA ** 2))
+    return (g / g.sum()).to(dtype=dtype, device=device)
+
+
+def check_image_pair(pred: torch.Tensor, target: torch.Tensor) -> None:
+    if pred.dim() != 4 or pred.shape[-1] != 3 or pred.shape != target.shape:
+        raise ValueError("image_metrics: pred and target must both be "
+                         f"(N,H,W,3), got {tuple(pred.shape)} and "
+                         f"{tuple(target.shape)}")
+    if pred.dtype != target.dtype:
+        raise ValueError("image_metrics: pred and target dtypes differ "
+                         f"({pred.dtype} vs {target.dtype})")
+    if pred.shape[1] < SSIM_WINDOW or pred.shape[2] < SSIM_WINDOW:
+        raise ValueError(f"image_metrics: H and W must be >= {SSIM_WINDOW} "
+                         f"(the SSIM window), got {tuple(pred.shape[1:3])}")
+
+
+def image_metrics(pred: torch.Tensor, target: torch.Tensor,
+                  quantize: bool = False
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """PSNR (dB) and SSIM per image of (N,H,W,3) pairs in [-1,1].
+
+    Per element u = clamp(x,-1,1)*0.5+0.5 (data_range 1); `quantize`
+    replaces pred's u with trunc(u*255)/255, the 8-bit value sample.py writes
+    to PNG, so the metrics equal those of the saved file. The target is left
+    alone: a dataset image holds 8-bit levels already, and truncating k/255
+    again would drop a quarter of the levels by one (k/255*255 < k in floating
+    point). PSNR = 10 log10(1/mse), +inf at mse 0. SSIM (Wang et al. 2004) per
+    channel with the separable 11-tap Gaussian window, population moments,
+    C1 = 0.01^2, C2 = 0.03^2, averaged over the valid (H-10)*(W-10) window
+    positions of the 3 channels (no padding). Works in the dtype it is
+    given (bf16/fp16 are upcast to fp32); returns two (N,) tensors."""
+    check_image_pair(pred, target)
+    dt = pred.dtype if pred.dtype in (torch.float32, torch.float64) \
+        else torch.float32
+
+    def prep(x, q):
+        u = x.to(dt).clamp(-1.0, 1.0) * 0.5 + 0.5
+        if q:
+            u = torch.trunc(u * 255.0) / 255.0
+        return u
+
+    x, y = prep(pred, quantize), prep(target, False)
+    N, H, W, _ = x.shape
+    mse = ((x - y) ** 2).mean(dim=(1, 2, 3))
+    psnr = 10.0 * torch.log10(1.0 / mse)
+
+    g = ssim_window(dt, x.device)
+    gh, gv = g.view(1, 1, 1, -1), g.view(1, 1, -1, 1)
+
+    def filt(t):
+        return F.conv2d(F.conv2d(t, gh), gv)
+
+    xc = x.permute(0, 3, 1, 2).reshape(N * 3, 1, H, W)
+    yc = y.permute(0, 3, 1, 2).reshape(N * 3, 1, H, W)
+    mu_x, mu_y = filt(xc), filt(yc)
+    var_x = filt(xc * xc) - mu_x * mu_x
+    var_y = filt(yc * yc) - mu_y * mu_y
+    cov = filt(xc * yc) - mu_x * mu_y
+    s = ((2.0 * mu_x * mu_y + SSIM_C1) * (2.0 * cov + SSIM_C2)
+         / ((mu_x * mu_x + mu_y * mu_y + SSIM_C1)
+            * (var_x + var_y + SSIM_C2)))
+    ssim = s.reshape(N, -1).mean(dim=1)
+    return psnr, ssim
