@@ -4,7 +4,7 @@
 // P from Q,K and the saved forward logsumexp, then runs 4 rocBLAS GEMMs.
 // Eager torch would materialize S and P in fp32 (~6 passes over B*H*L*L);
 // these two kernels do it in one pass each, bf16 in/out, fp32 math:
-//   attn_p_from_lse: P = exp(S*scale - lse)            (S = QK^T, bf16)
+//   attn_p_from_lse: P = exp(S*scale - lse)            (S = QK^T, bf16 or fp32)
 //   attn_ds:         dS = scale * P * (dP - delta)     (delta = rowsum(dO*O))
 
 #include <torch/extension.h>
@@ -15,7 +15,8 @@
 namespace {
 
 // p[b,h,i,j] = exp(s[b,h,i,j]*scale - lse[b,i,h])
-__global__ void attn_p_kernel(const bf16* __restrict__ s,
+template <typename ST>
+__global__ void attn_p_kernel(const ST* __restrict__ s,
                               const float* __restrict__ lse,  // (B,L,H)
                               bf16* __restrict__ p,
                               float scale, int B, int H, int L, int Lk) {
@@ -23,7 +24,7 @@ __global__ void attn_p_kernel(const bf16* __restrict__ s,
   const long stride = (long)gridDim.x * blockDim.x * 8;
   for (long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8;
        i0 < total; i0 += stride) {
-    Pack<bf16, 8> vs = pload<bf16, 8>(s + i0);
+    Pack<ST, 4> vs[2] = {pload<ST, 4>(s + i0), pload<ST, 4>(s + i0 + 4)};
     const long row = i0 / Lk;        // (b*H + h)*L + i
     const int qi = (int)(row % L);
     const int h = (int)((row / L) % H);
@@ -32,7 +33,7 @@ __global__ void attn_p_kernel(const bf16* __restrict__ s,
     Pack<bf16, 8> vp;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      from_f32(__expf(to_f32(vs.v[j]) * scale - l), vp.v[j]);
+      from_f32(__expf(to_f32(vs[j >> 2].v[j & 3]) * scale - l), vp.v[j]);
     }
     pstore<bf16, 8>(p + i0, vp);
   }
@@ -64,17 +65,27 @@ __global__ void attn_ds_kernel(const bf16* __restrict__ p,
 
 torch::Tensor attn_p_from_lse(torch::Tensor s, torch::Tensor lse,
                               double scale) {
+  const bool f32 = s.scalar_type() == torch::kFloat;
   TORCH_CHECK(s.is_cuda() && s.is_contiguous()
-              && s.scalar_type() == torch::kBFloat16);
+              && (f32 || s.scalar_type() == torch::kBFloat16));
   const int B = s.size(0), H = s.size(1), L = s.size(2), Lk = s.size(3);
   TORCH_CHECK(Lk % 8 == 0);
-  auto p = torch::empty_like(s);
+  TORCH_CHECK(lse.is_contiguous() && lse.scalar_type() == torch::kFloat
+              && lse.numel() == (long)B * L * H);
+  auto p = torch::empty({B, H, L, Lk}, s.options().dtype(torch::kBFloat16));
   const long total = s.numel() / 8;
   const int grid = (int)std::min<long>((total + 255) / 256, 8192);
   auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(attn_p_kernel, dim3(grid), dim3(256), 0, stream,
-      reinterpret_cast<const bf16*>(s.data_ptr()), lse.data_ptr<float>(),
-      reinterpret_cast<bf16*>(p.data_ptr()), (float)scale, B, H, L, Lk);
+  if (f32) {
+    hipLaunchKernelGGL(attn_p_kernel<float>, dim3(grid), dim3(256), 0,
+        stream, s.data_ptr<float>(), lse.data_ptr<float>(),
+        reinterpret_cast<bf16*>(p.data_ptr()), (float)scale, B, H, L, Lk);
+  } else {
+    hipLaunchKernelGGL(attn_p_kernel<bf16>, dim3(grid), dim3(256), 0,
+        stream, reinterpret_cast<const bf16*>(s.data_ptr()),
+        lse.data_ptr<float>(), reinterpret_cast<bf16*>(p.data_ptr()),
+        (float)scale, B, H, L, Lk);
+  }
   return p;
 }
 

@@ -291,7 +291,9 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
   s.kv_swap = kv_swap ? 1 : 0;
   TORCH_CHECK(!kv_swap || B % 2 == 0, "kv_swap pairs batches (b, b^1)");
 
-  auto out = torch::empty_like(q);
+  // the kernel writes out as a contiguous (B,L,H,D) array; empty_like would
+  // keep the strides of a dense permuted q (e.g. an (L,B,H,D) transpose)
+  auto out = torch::empty({B, L, H, D}, q.options());
   auto lse = torch::empty({B, L, H}, q.options().dtype(torch::kFloat));
   const int grid = B * H * (L / 64);
   auto stream = at::hip::getCurrentHIPStream();

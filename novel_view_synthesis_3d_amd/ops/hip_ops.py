@@ -437,6 +437,11 @@ def frame_conv3x3_residual(x, weight, bias, residual, res_scale):
 # backward (rocBLAS batched matmuls — the "plain library GEMM" path).
 # ---------------------------------------------------------------------------
 
+# 1/sqrt(d) as attn_fwd.hip forms it (fp32 sqrt, fp32 divide)
+_ATTN_SCALE = {d: float(1.0 / torch.tensor(float(d)).sqrt())
+               for d in (32, 128)}
+
+
 class _Attention(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
@@ -481,8 +486,20 @@ class _Attention(torch.autograd.Function):
         vt = v.permute(0, 2, 1, 3)
         dob = do.to(q.dtype).permute(0, 2, 1, 3)
         # recompute P in ONE pass (bf16 GEMM + fused exp(S*scale - lse))
-        s = torch.matmul(qt, kt.transpose(-1, -2)).contiguous()
-        p = _OPS.attn_p_from_lse(s, lse, scale)        # (B,H,L,Lk) bf16
+        if D in (32, 128):
+            # 1/sqrt(d) is no bf16 value here: the saved lse belongs to the
+            # forward's logits bf16(q*scale).k, which scaling q.k afterwards
+            # misses by |logit| * 1.1e-4 (P = 1.016 at logit 136). Form the
+            # same logits (a bf16 tensor times a Python scalar is computed in
+            # fp32 and rounded once) and keep them in fp32.
+            qs = torch.mul(qt, _ATTN_SCALE[D], out=q.new_empty((B, H, L, D)))
+            s = torch.bmm(qs.view(B * H, L, D),
+                          kt.reshape(B * H, Lk, D).transpose(1, 2),
+                          out_dtype=torch.float32).view(B, H, L, Lk)
+            p = _OPS.attn_p_from_lse(s, lse, 1.0)
+        else:
+            s = torch.matmul(qt, kt.transpose(-1, -2)).contiguous()
+            p = _OPS.attn_p_from_lse(s, lse, scale)    # (B,H,L,Lk) bf16
         dv = torch.matmul(p.transpose(-1, -2), dob)
         dp = torch.matmul(dob, vt.transpose(-1, -2)).contiguous()
         delta = _OPS.attn_delta(do.to(q.dtype).contiguous(), o)
