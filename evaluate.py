@@ -9,6 +9,9 @@ with the ground truth.
         --folder cars_test --steps 256 --input-view 64 --num-targets 16 \
         --batch-objects 4 --out results/eval
 
+Few-step solvers: --solver {ddpm,ddim,dpmpp2m} --spacing {uniform,logsnr}
+[--eta E], e.g. --solver dpmpp2m --spacing logsnr --steps 32.
+
 Writes OUT/metrics.json (aggregate, per-instance values, settings) and prints
 one summary line. Model config, sidelength and EMA weights come from the
 checkpoint as in sample.py.
@@ -21,6 +24,9 @@ import os
 import torch
 
 from novel_view_synthesis_3d_amd.config import XUNetConfig
+from novel_view_synthesis_3d_amd.diffusion.solvers import (
+    add_solver_args, check_solver_cli,
+)
 from novel_view_synthesis_3d_amd.engine import checkpoint as ckpt
 from novel_view_synthesis_3d_amd.engine.evaluate import (
     MODES, Evaluator, to_serialisable,
@@ -40,6 +46,7 @@ def main() -> None:
                     help="image sidelength; default: read from checkpoint")
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--guidance", type=float, default=3.0)
+    add_solver_args(ap)
     ap.add_argument("--input-view", type=int, default=64,
                     help="index of the conditioning observation")
     ap.add_argument("--num-targets", type=int, default=None,
@@ -67,6 +74,7 @@ def main() -> None:
                          "the checkpoint carries them)")
     ap.add_argument("--out", default="./results/eval")
     args = ap.parse_args()
+    check_solver_cli(ap, args)
 
     device = "cuda" if torch.cuda.is_available() else "cpu"
     payload = torch.load(args.checkpoint, map_location=device,
@@ -93,7 +101,8 @@ def main() -> None:
                    max_bank=args.max_bank,
                    use_graph=(device == "cuda" and not args.no_graph),
                    batch_objects=args.batch_objects, seed=args.seed,
-                   quantize=args.quantize)
+                   quantize=args.quantize, solver=args.solver,
+                   spacing=args.spacing, eta=args.eta)
     os.makedirs(args.out, exist_ok=True)
     result = ev.evaluate(
         args.folder, sidelength, input_view=args.input_view,

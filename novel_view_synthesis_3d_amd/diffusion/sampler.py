@@ -13,7 +13,11 @@ Redesign:
     posterior coefficients between consecutive kept timesteps,
   * logsnr fed at step t is logsnr(t/T) — the level the model saw in
     training. `legacy_logsnr=True` reproduces reference D5 (uses
-    logsnr((t+1)/T)).
+    logsnr((t+1)/T)),
+  * `solver` / `spacing` / `eta` select a few-step solver (ddim, dpmpp2m)
+    and the timestep spacing from diffusion/solvers.py; the step is then
+    `ops.solver_cfg_step`, which carries the previous x0 prediction. The
+    defaults keep the ancestral path below unchanged.
 """
 
 from __future__ import annotations
@@ -25,16 +29,22 @@ import torch
 from novel_view_synthesis_3d_amd.diffusion.schedules import (
     DiffusionSchedule, logsnr_schedule_cosine,
 )
+from novel_view_synthesis_3d_amd.diffusion.solvers import (
+    check_solver_args, device_tables, solver_tables,
+)
 
 
 class DDPMSampler:
     def __init__(self, model, schedule: Optional[DiffusionSchedule] = None,
                  num_steps: int = 1000, guidance_weight: float = 3.0,
                  clip_denoised: bool = True, legacy_logsnr: bool = False,
-                 use_graph: bool = False):
+                 use_graph: bool = False, solver: str = "ddpm",
+                 spacing: str = "uniform", eta: float = 0.0):
+        check_solver_args(solver, spacing, float(eta))
         self.model = model
         self.schedule = schedule or DiffusionSchedule(1000)
         self.num_steps = num_steps
+        self.solver, self.spacing, self.eta = solver, spacing, float(eta)
         self.w = guidance_weight
         self.clip_denoised = clip_denoised
         self.legacy_logsnr = legacy_logsnr
@@ -76,6 +86,30 @@ class DDPMSampler:
             [logsnr_schedule_cosine(float(x)) for x in u], dtype=torch.float64)
         return {k: v.to(device=device, dtype=torch.float32) for k, v in tab.items()}
 
+    @property
+    def default_solver(self) -> bool:
+        """ddpm on uniform timesteps: the path of `_step_tables` and the
+        ancestral step; anything else goes through diffusion/solvers.py and
+        ops.solver_cfg_step."""
+        return (self.solver == "ddpm" and self.spacing == "uniform"
+                and self.eta == 0.0)
+
+    def _solver_state(self, z: torch.Tensor) -> Dict:
+        """Tables and static buffers of the solver step for a latent like z:
+        `hist` only for a multistep solver, `noise` (a flag) only when some
+        sigma is nonzero — a deterministic solver issues no randn."""
+        tab64 = solver_tables(self.schedule, self.num_steps, self.solver,
+                              spacing=self.spacing, eta=self.eta,
+                              legacy_logsnr=self.legacy_logsnr)
+        step = torch.zeros(1, dtype=torch.long, device=z.device)
+        return {
+            "tab": device_tables(tab64, z.device),
+            "hist": (torch.zeros_like(z)
+                     if bool((tab64["coef_hist"] != 0).any()) else None),
+            "noise": bool((tab64["sigma"] != 0).any()),
+            "step_scratch": torch.zeros_like(step),
+        }
+
     # -----------------------------------------------------------------
     def _make_cond2(self, cond: Dict[str, torch.Tensor]):
         """Duplicate conditioning along batch for the batched CFG forward."""
@@ -87,8 +121,9 @@ class DDPMSampler:
         return c2, mask
 
     def _step(self, z: torch.Tensor, idx: torch.Tensor, cond2, mask, tab,
-              pose_cache=None) -> None:
-        """One in-place ancestral step; everything device-side."""
+              pose_cache=None, solver_state=None) -> None:
+        """One in-place step; everything device-side. Ancestral by default;
+        with `solver_state` (and its tables as `tab`) the solver step."""
         B = z.shape[0]
         logsnr = tab["logsnr"].index_select(0, idx).expand(2 * B)
         batch = dict(cond2)
@@ -99,6 +134,16 @@ class DDPMSampler:
                 out = self.model(batch, mask, pose_cache=pose_cache)
         else:
             out = self.model(batch, mask, pose_cache=pose_cache)
+        if solver_state is not None:
+            from novel_view_synthesis_3d_amd import ops
+            noise = torch.randn_like(z) if solver_state["noise"] else None
+            ops.solver_cfg_step(
+                z, solver_state["hist"], out, noise, tab["sqrt_recip_abar"],
+                tab["sqrt_recipm1_abar"], tab["coef_z"], tab["coef_x0"],
+                tab["coef_hist"], tab["sigma"], idx, self.w,
+                self.clip_denoised,
+                step_scratch=solver_state["step_scratch"])
+            return
         out = out.to(torch.float32)
         eps = (1.0 + self.w) * out[:B] - self.w * out[B:]
 
@@ -131,7 +176,8 @@ class DDPMSampler:
             z = (z_init.clone() if z_init is not None
                  else torch.empty_like(x).normal_(generator=generator))
             cond2, mask = self._make_cond2(cond)
-            tab = self._step_tables(device)
+            sst = None if self.default_solver else self._solver_state(z)
+            tab = self._step_tables(device) if sst is None else sst["tab"]
             idx = torch.zeros(1, dtype=torch.long, device=device)
 
             # Pose conditioning is step-invariant: compute once, outside any
@@ -145,16 +191,17 @@ class DDPMSampler:
                 pose_cache = cp.pose_features(cond2, mask)
 
             if self.use_graph and device.type == "cuda":
-                self._run_graphed(z, idx, cond2, mask, tab, pose_cache)
+                self._run_graphed(z, idx, cond2, mask, tab, pose_cache, sst)
             else:
                 for _ in range(self.num_steps):
-                    self._step(z, idx, cond2, mask, tab, pose_cache)
+                    self._step(z, idx, cond2, mask, tab, pose_cache, sst)
             return z
         finally:
             self.model.train(was_training)
 
     # -----------------------------------------------------------------
-    def _run_graphed(self, z, idx, cond2, mask, tab, pose_cache) -> None:
+    def _run_graphed(self, z, idx, cond2, mask, tab, pose_cache,
+                     solver_state=None) -> None:
         """Capture one sampler step as a hipGraph and replay it num_steps
         times. Per-step state (z, idx) lives in the captured buffers; RNG is
         graph-safe (torch captures the philox offset)."""
@@ -166,7 +213,8 @@ class DDPMSampler:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):  # warmup, required before capture
             for _ in range(n_warm):
-                self._step(z, idx, cond2, mask, tab, pose_cache)
+                self._step(z, idx, cond2, mask, tab, pose_cache,
+                           solver_state)
         torch.cuda.current_stream().wait_stream(s)
         done_warmup = int(idx.item())
         if self.num_steps - done_warmup <= 0:
@@ -176,7 +224,7 @@ class DDPMSampler:
         with torch.cuda.graph(graph):
             # capture RECORDS the step without executing it; z/idx advance
             # only on replay
-            self._step(z, idx, cond2, mask, tab, pose_cache)
+            self._step(z, idx, cond2, mask, tab, pose_cache, solver_state)
         for _ in range(self.num_steps - done_warmup):
             graph.replay()
 
@@ -249,6 +297,16 @@ class StochasticConditioningSampler:
                      0, st["step"]).expand(2 * B)}
         with self._ctx(z.device):
             out = self.model(batch, st["mask"], pose_cache=st["cache"])
+        if st["solver_step"]:
+            noise = torch.randn_like(z) if st["draw_noise"] else None
+            ops.solver_cfg_step(
+                z, st["hist"], out, noise, tab["sqrt_recip_abar"],
+                tab["sqrt_recipm1_abar"], tab["coef_z"], tab["coef_x0"],
+                tab["coef_hist"], tab["sigma"], st["step"], st["w"],
+                st["clip"], st["noise_scale"], u=st["u"], k=st["k"],
+                bank_img=st["bank_img"], x=st["x2"],
+                step_scratch=st["step_scratch"])
+            return
         noise = torch.randn_like(z)
         ops.ddpm_cfg_step(z, out, noise, tab["sqrt_recip_abar"],
                           tab["sqrt_recipm1_abar"], tab["mean_c1"],
@@ -339,7 +397,9 @@ class StochasticConditioningSampler:
                      seed: Optional[int] = None,
                      z_init: Optional[torch.Tensor] = None,
                      use_graph: bool = False, stochastic: bool = True,
-                     on_view_start=None) -> torch.Tensor:
+                     on_view_start=None, solver: str = "ddpm",
+                     spacing: str = "uniform",
+                     eta: float = 0.0) -> torch.Tensor:
         """x0 (B,H,W,3) input view with pose R0 (B,3,3), t0 (B,3); K
         (B,3,3); target_R (N,B,3,3), target_t (N,B,3). Returns (N,B,H,W,3).
 
@@ -347,7 +407,9 @@ class StochasticConditioningSampler:
         and the step noise come from the global RNG exactly as in
         DDPMSampler. `z_init` is (B,H,W,3) (used for every view) or
         (N,B,H,W,3). `stochastic=False` always conditions on the input
-        view. `on_view_start(n, state)` runs after view n's state is set."""
+        view. `on_view_start(n, state)` runs after view n's state is set.
+        `solver`, `spacing`, `eta` as in DDPMSampler; a solver whose sigma
+        table is all zero (ddim with eta 0, dpmpp2m) draws no step noise."""
         model = self.model
         was_training = model.training
         model.eval()
@@ -363,7 +425,8 @@ class StochasticConditioningSampler:
                 raise ValueError("stochastic=False needs the input view to "
                                  "stay in the bank (max_bank too small)")
             helper = DDPMSampler(model, self.schedule, num_steps=S,
-                                 legacy_logsnr=self.legacy_logsnr)
+                                 legacy_logsnr=self.legacy_logsnr,
+                                 solver=solver, spacing=spacing, eta=eta)
             cfg = model.cfg
             E, L = cfg.emb_ch, cfg.num_resolutions
             act = (torch.bfloat16 if device.type == "cuda" and self.autocast
@@ -395,7 +458,14 @@ class StochasticConditioningSampler:
                 "bank_img": torch.zeros(Kcap, B, H, W, 3, **f32),
                 "step": step, "step_scratch": torch.zeros_like(step),
                 "k": k, "u": u, "cache": cache,
+                "solver_step": False, "hist": None, "draw_noise": True,
             }
+            if not helper.default_solver:
+                # hist is static like z: captured in the graph and never
+                # reset per view (coef_hist[0] = 0 keeps it out of step 0)
+                sst = helper._solver_state(st["z"])
+                st.update(solver_step=True, tab=sst["tab"],
+                          hist=sst["hist"], draw_noise=sst["noise"])
             # the null source feature is camera-independent: computed once
             _, null0 = self._frame_features(st, R0, t0, 0)
             cache.null = [nf.contiguous() for nf in null0]

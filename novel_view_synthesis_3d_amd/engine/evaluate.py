@@ -24,6 +24,7 @@ from novel_view_synthesis_3d_amd.data.srn import SceneInstanceDataset
 from novel_view_synthesis_3d_amd.diffusion.sampler import (
     StochasticConditioningSampler,
 )
+from novel_view_synthesis_3d_amd.diffusion.solvers import check_solver_args
 
 MODES = ("autoregressive", "independent")
 
@@ -54,15 +55,19 @@ class Evaluator:
     """mode="autoregressive": every denoising step of a view is conditioned
     on a view drawn from the input plus the views generated so far (3DiM
     stochastic conditioning); mode="independent": always on the input view.
-    `quantize` evaluates the 8-bit values sample.py writes to PNG."""
+    `quantize` evaluates the 8-bit values sample.py writes to PNG. `solver`,
+    `spacing` and `eta` go to the sampler (diffusion/solvers.py)."""
 
     def __init__(self, model, num_steps: int, guidance_weight: float = 3.0,
                  mode: str = "autoregressive",
                  max_bank: Optional[int] = None, use_graph: bool = False,
                  batch_objects: int = 1, seed: int = 0,
-                 quantize: bool = False):
+                 quantize: bool = False, solver: str = "ddpm",
+                 spacing: str = "uniform", eta: float = 0.0):
         if mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+        check_solver_args(solver, spacing, float(eta))
+        self.solver, self.spacing, self.eta = solver, spacing, float(eta)
         if batch_objects < 1:
             raise ValueError("batch_objects must be >= 1")
         self.model = model
@@ -165,7 +170,8 @@ class Evaluator:
                 guidance_weight=self.guidance_weight, clip_denoised=True,
                 seed=self.seed + bi,
                 use_graph=self.use_graph and device.type == "cuda",
-                stochastic=self.mode == "autoregressive")
+                stochastic=self.mode == "autoregressive",
+                solver=self.solver, spacing=self.spacing, eta=self.eta)
             out = out.clamp(-1.0, 1.0)
             H, W = out.shape[2:4]
             psnr, ssim = ops.image_metrics(out.reshape(N * B, H, W, 3),
@@ -206,7 +212,8 @@ class Evaluator:
                 "guidance_weight": self.guidance_weight, "mode": self.mode,
                 "max_bank": self.max_bank, "use_graph": self.use_graph,
                 "batch_objects": self.batch_objects, "seed": self.seed,
-                "quantize": self.quantize,
+                "quantize": self.quantize, "solver": self.solver,
+                "spacing": self.spacing, "eta": self.eta,
             },
         }
         if return_images:

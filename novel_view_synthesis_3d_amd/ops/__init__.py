@@ -180,6 +180,24 @@ def ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma, step, u, k,
                              k, bank_img, x, w, clip, noise_scale)
 
 
+def solver_cfg_step(z, hist, out, noise, c_a, c_b, coef_z, coef_x0, coef_hist,
+                    sigma, step, w: float, clip: bool,
+                    noise_scale: float = 1.0, *, u=None, k=None,
+                    bank_img=None, x=None, step_scratch=None) -> None:
+    """CFG combine + one step of a solver of diffusion/solvers.py in place on
+    z; hist (or None) carries the previous step's x0, noise may be None.
+    Advances `step`; with u, k, bank_img and x also writes the next step's
+    model input x from the image bank, as ddpm_cfg_step does."""
+    if _use_hip(z, "solver_cfg_step"):
+        return _HIP_MOD.solver_cfg_step(
+            z, hist, out, noise, c_a, c_b, coef_z, coef_x0, coef_hist, sigma,
+            step, w, clip, noise_scale, u=u, k=k, bank_img=bank_img, x=x,
+            step_scratch=step_scratch)
+    return ref.solver_cfg_step(z, hist, out, noise, c_a, c_b, coef_z, coef_x0,
+                               coef_hist, sigma, step, w, clip, noise_scale,
+                               u=u, k=k, bank_img=bank_img, x=x)
+
+
 # ---------------------------------------------------------------------------
 # Image quality metrics (ops/hip/image_metrics.hip)
 # ---------------------------------------------------------------------------

@@ -70,6 +70,17 @@ void ddpm_cfg_step(torch::Tensor z, torch::Tensor out, torch::Tensor noise,
                    torch::Tensor u, torch::Tensor kvalid,
                    torch::Tensor bank_img, torch::Tensor x, double w,
                    bool clip, double noise_scale);
+void solver_cfg_step(torch::Tensor z, c10::optional<torch::Tensor> hist,
+                     torch::Tensor out, c10::optional<torch::Tensor> noise,
+                     torch::Tensor t_ca, torch::Tensor t_cb,
+                     torch::Tensor t_cz, torch::Tensor t_cx,
+                     torch::Tensor t_ch, torch::Tensor t_sigma,
+                     torch::Tensor step, torch::Tensor step_next,
+                     c10::optional<torch::Tensor> u,
+                     c10::optional<torch::Tensor> kvalid,
+                     c10::optional<torch::Tensor> bank_img,
+                     c10::optional<torch::Tensor> x, double w, bool clip,
+                     double noise_scale);
 std::vector<torch::Tensor> image_metrics(torch::Tensor pred,
                                          torch::Tensor target,
                                          bool quantize);
@@ -123,6 +134,11 @@ TORCH_LIBRARY(nvs3d, m) {
         "Tensor(b!) step, Tensor(c!) step_next, Tensor u, Tensor kvalid, "
         "Tensor bank_img, Tensor(d!) x, float w, bool clip, "
         "float noise_scale) -> ()");
+  m.def("solver_cfg_step(Tensor(a!) z, Tensor(b!)? hist, Tensor out, "
+        "Tensor? noise, Tensor t_ca, Tensor t_cb, Tensor t_cz, Tensor t_cx, "
+        "Tensor t_ch, Tensor t_sigma, Tensor(c!) step, Tensor(d!) step_next, "
+        "Tensor? u, Tensor? kvalid, Tensor? bank_img, Tensor(e!)? x, "
+        "float w, bool clip, float noise_scale) -> ()");
   m.def("image_metrics(Tensor pred, Tensor target, bool quantize) "
         "-> Tensor[]");
   m.def("image_metrics_tile() -> int", image_metrics_tile);
@@ -152,5 +168,6 @@ TORCH_LIBRARY_IMPL(nvs3d, CUDA, m) {
   m.impl("add_scale", add_scale);
   m.impl("cond_emb_select", cond_emb_select);
   m.impl("ddpm_cfg_step", ddpm_cfg_step);
+  m.impl("solver_cfg_step", solver_cfg_step);
   m.impl("image_metrics", image_metrics);
 }

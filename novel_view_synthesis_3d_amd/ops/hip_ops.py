@@ -664,6 +664,23 @@ def ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma, step, u, k,
                            float(w), bool(clip), float(noise_scale))
 
 
+HAS |= {"solver_cfg_step"}
+
+
+def solver_cfg_step(z, hist, out, noise, c_a, c_b, coef_z, coef_x0, coef_hist,
+                    sigma, step, w, clip, noise_scale=1.0, *, u=None, k=None,
+                    bank_img=None, x=None, step_scratch=None) -> None:
+    """hist and noise may be None; u, k, bank_img, x come together or not at
+    all. `step_scratch` as in ddpm_cfg_step."""
+    if step_scratch is None:
+        step_scratch = torch.empty_like(step)
+    with torch.no_grad():
+        _OPS.solver_cfg_step(z, hist, out.contiguous(), noise, c_a, c_b,
+                             coef_z, coef_x0, coef_hist, sigma, step,
+                             step_scratch, u, k, bank_img, x, float(w),
+                             bool(clip), float(noise_scale))
+
+
 # ---------------------------------------------------------------------------
 # Fused PSNR + SSIM (image_metrics.hip); inference only
 # ---------------------------------------------------------------------------

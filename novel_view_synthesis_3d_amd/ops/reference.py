@@ -252,6 +252,52 @@ def ddpm_cfg_step(z: torch.Tensor, out: torch.Tensor, noise: torch.Tensor,
     x.copy_(torch.where(live, torch.cat([nxt, nxt], dim=0), x))
 
 
+def solver_cfg_step(z: torch.Tensor, hist: Optional[torch.Tensor],
+                    out: torch.Tensor, noise: Optional[torch.Tensor],
+                    c_a: torch.Tensor, c_b: torch.Tensor,
+                    coef_z: torch.Tensor, coef_x0: torch.Tensor,
+                    coef_hist: torch.Tensor, sigma: torch.Tensor,
+                    step: torch.Tensor, w: float, clip: bool,
+                    noise_scale: float = 1.0, *, u=None, k=None,
+                    bank_img=None, x=None) -> None:
+    """One post-network step of a solver of diffusion/solvers.py, in place on
+    z, hist, step and (with the bank arguments) x.
+
+    eps = (1+w) out[:B] - w out[B:];  x0 = c_a z - c_b eps (clamped to
+    [-1,1] if clip);  z <- coef_z z + coef_x0 x0 + coef_hist hist
+    + noise_scale sigma noise;  hist <- x0;  step += 1, coefficients taken
+    from the (S,) tables at `step`. hist enters only where coef_hist is
+    nonzero, so whatever it holds at the first step of a view (stale values,
+    NaN) never reaches z; hist=None is a first-order solver, noise=None a
+    deterministic one. With u, k, bank_img and x the next step's x is
+    gathered as in ddpm_cfg_step."""
+    B = z.shape[0]
+    S = coef_z.shape[0]
+    s = step.reshape(1)
+    o = out.to(torch.float32)
+    eps = (1.0 + w) * o[:B] - w * o[B:]
+    x0 = c_a.index_select(0, s) * z - c_b.index_select(0, s) * eps
+    if clip:
+        x0 = x0.clamp(-1.0, 1.0)
+    new = coef_z.index_select(0, s) * z + coef_x0.index_select(0, s) * x0
+    if hist is not None:
+        ch = coef_hist.index_select(0, s)
+        # where(), not a product: 0 * NaN is NaN (and no host branch)
+        new = new + torch.where(ch != 0, ch * hist, torch.zeros_like(hist))
+        hist.copy_(x0)
+    if noise is not None:
+        new = new + (noise_scale * sigma.index_select(0, s)) * noise
+    z.copy_(new)
+    step.add_(1)
+    if bank_img is None:
+        return
+    s1 = step.reshape(1).clamp(max=S - 1)
+    idx = stochastic_index(u.index_select(0, s1)[0], k)
+    nxt = bank_img[idx, torch.arange(B, device=z.device)]
+    live = (step.reshape(()) < S)
+    x.copy_(torch.where(live, torch.cat([nxt, nxt], dim=0), x))
+
+
 # ---------------------------------------------------------------------------
 # Image quality metrics (oracle for ops/hip/image_metrics.hip)
 # ---------------------------------------------------------------------------

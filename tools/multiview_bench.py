@@ -4,6 +4,11 @@ model/batch/steps of tools/sample_bench.py (full 128x128, CFG w=3, hipGraph
 step), N views per object. Prints one JSON line.
 
     python tools/multiview_bench.py --steps 256 --batch 64 --views 2
+    python tools/multiview_bench.py --steps 32 --batch 64 --views 2 \
+        --solver dpmpp2m --spacing logsnr --repeats 3
+
+Reports ms/step and s/view (the median of --repeats timed passes, every pass
+listed in ms_per_step_all).
 """
 
 import argparse
@@ -22,6 +27,9 @@ from novel_view_synthesis_3d_amd.data.synthetic import (
 from novel_view_synthesis_3d_amd.diffusion.sampler import (
     StochasticConditioningSampler,
 )
+from novel_view_synthesis_3d_amd.diffusion.solvers import (
+    add_solver_args, check_solver_cli,
+)
 from novel_view_synthesis_3d_amd.models.xunet import XUNet
 
 
@@ -34,7 +42,11 @@ def main():
     ap.add_argument("--views", type=int, default=2)
     ap.add_argument("--max-bank", type=int, default=None)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed passes after the warm-up pass")
+    add_solver_args(ap)
     args = ap.parse_args()
+    check_solver_cli(ap, args)
     assert torch.cuda.is_available()
 
     torch.manual_seed(0)
@@ -53,23 +65,30 @@ def main():
         return sampler.sample_views(
             cond["x"], cond["R1"], cond["t1"], cond["K"], tR, tt,
             num_steps=args.steps, guidance_weight=3.0, clip_denoised=True,
-            seed=0, use_graph=not args.no_graph)
+            seed=0, use_graph=not args.no_graph, solver=args.solver,
+            spacing=args.spacing, eta=args.eta)
 
     # warmup pass (library autotuning, allocator); each call captures its
     # own graph, so the timed pass includes one capture like sample_bench's
     out = run()
     torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = run()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    times = []
+    for _ in range(max(1, args.repeats)):
+        t0 = time.perf_counter()
+        out = run()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    dt = sorted(times)[len(times) // 2]
     assert torch.isfinite(out).all()
     total_steps = args.steps * args.views
     print(json.dumps({
         "metric": "stochastic-conditioning multi-view sampling (1 GPU)",
         "ms_per_step": round(dt / total_steps * 1000, 2),
+        "ms_per_step_all": [round(t / total_steps * 1000, 2) for t in times],
+        "sec_per_view": round(dt / args.views, 3),
         "views_per_sec": round(args.batch * args.views / dt, 3),
         "sec_total": round(dt, 2),
+        "solver": args.solver, "spacing": args.spacing, "eta": args.eta,
         "batch": args.batch, "steps": args.steps, "views": args.views,
         "graph": not args.no_graph, "graph_captures": sampler.num_captures,
         "model": args.model, "sidelength": args.sidelength,
