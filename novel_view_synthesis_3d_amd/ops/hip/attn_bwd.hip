@@ -20,8 +20,11 @@
 // scatter tiles where a fragment needs the contraction dim contiguous,
 // per-wave LDS tiles to convert C-layout P/ds into A-fragments.
 //
-// Supported: d in {16, 32, 64, 128}, L % 128 == 0 (q and kv); the d=256 /
-// short-L shapes keep the GEMM-recompute fallback (ops/hip_ops.py).
+// Supported: d in {16, 32, 64, 128, 256}, L % 128 == 0 (q and kv). At
+// d = 256 the dkv template does not fit in LDS; that shape has a dkv kernel
+// of its own in attn_bwd_d256.hip (row-major images + transpose reads) and
+// uses the dq template below. Short-L shapes keep the GEMM-recompute
+// fallback (ops/hip_ops.py).
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -578,6 +581,14 @@ ABwdShape make_shape(const torch::Tensor& q, const torch::Tensor& k,
 
 }  // namespace
 
+// attn_bwd_d256.hip
+void attn_bwd_dkv256_launch(const torch::Tensor& q, const torch::Tensor& k,
+                            const torch::Tensor& v, const torch::Tensor& dout,
+                            const torch::Tensor& lse,
+                            const torch::Tensor& delta, torch::Tensor& dk,
+                            torch::Tensor& dv, bool kv_swap,
+                            hipStream_t stream);
+
 torch::Tensor attn_delta(torch::Tensor dout, torch::Tensor o) {
   TORCH_CHECK(dout.is_cuda() && dout.is_contiguous() && o.is_contiguous());
   const int B = dout.size(0), L = dout.size(1), H = dout.size(2),
@@ -613,8 +624,8 @@ std::vector<torch::Tensor> attn_bwd_fused(torch::Tensor q, torch::Tensor k,
               "kv_swap pairs batches (b, b^1)");
   TORCH_CHECK(s.L % 128 == 0 && s.Lk % 128 == 0,
               "L must be a multiple of 128");
-  TORCH_CHECK(s.D == 16 || s.D == 32 || s.D == 64 || s.D == 128,
-              "unsupported head dim for fused bwd: ", s.D);
+  TORCH_CHECK(s.D == 16 || s.D == 32 || s.D == 64 || s.D == 128
+              || s.D == 256, "unsupported head dim for fused bwd: ", s.D);
 
   auto dq = torch::empty({s.B, s.L, s.H, s.D},
                          q.options().layout(torch::kStrided));
@@ -622,6 +633,18 @@ std::vector<torch::Tensor> attn_bwd_fused(torch::Tensor q, torch::Tensor k,
   auto dv = torch::empty({s.B, s.Lk, s.H, s.D}, dq.options());
   auto stream = at::hip::getCurrentHIPStream();
 
+#define LAUNCH_DQ(DV)                                                      \
+  {                                                                        \
+    const size_t lds_q = (size_t)3 * KB2 * DV * 2 + 4 * 16 * KB2 * 2;      \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<DV>),                           \
+        dim3(s.B * s.H * (s.L / QTB)), dim3(256), lds_q, stream,           \
+        reinterpret_cast<const bf16*>(q.data_ptr()),                       \
+        reinterpret_cast<const bf16*>(k.data_ptr()),                       \
+        reinterpret_cast<const bf16*>(v.data_ptr()),                       \
+        reinterpret_cast<const bf16*>(dout.data_ptr()),                    \
+        lse.data_ptr<float>(), delta.data_ptr<float>(),                    \
+        reinterpret_cast<bf16*>(dq.data_ptr()), s);                        \
+  }
 #define LAUNCH_BWD(DV)                                                     \
   {                                                                        \
     const size_t lds_kv = 2 * ((size_t)4 * QTB * DV * 2 + 2 * QTB * 4)    \
@@ -635,22 +658,20 @@ std::vector<torch::Tensor> attn_bwd_fused(torch::Tensor q, torch::Tensor k,
         lse.data_ptr<float>(), delta.data_ptr<float>(),                    \
         reinterpret_cast<bf16*>(dk.data_ptr()),                            \
         reinterpret_cast<bf16*>(dv.data_ptr()), s);                        \
-    const size_t lds_q = (size_t)3 * KB2 * DV * 2 + 4 * 16 * KB2 * 2;      \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DV>),                           \
-        dim3(s.B * s.H * (s.L / QTB)), dim3(256), lds_q, stream,           \
-        reinterpret_cast<const bf16*>(q.data_ptr()),                       \
-        reinterpret_cast<const bf16*>(k.data_ptr()),                       \
-        reinterpret_cast<const bf16*>(v.data_ptr()),                       \
-        reinterpret_cast<const bf16*>(dout.data_ptr()),                    \
-        lse.data_ptr<float>(), delta.data_ptr<float>(),                    \
-        reinterpret_cast<bf16*>(dq.data_ptr()), s);                        \
+    LAUNCH_DQ(DV)                                                          \
   }
   switch (s.D) {
     case 16: LAUNCH_BWD(16); break;
     case 32: LAUNCH_BWD(32); break;
     case 64: LAUNCH_BWD(64); break;
     case 128: LAUNCH_BWD(128); break;
+    case 256:
+      attn_bwd_dkv256_launch(q, k, v, dout, lse, delta, dk, dv, kv_swap,
+                             stream);
+      LAUNCH_DQ(256)
+      break;
   }
 #undef LAUNCH_BWD
+#undef LAUNCH_DQ
   return {dq, dk, dv};
 }

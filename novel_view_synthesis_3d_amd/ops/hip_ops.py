@@ -433,8 +433,8 @@ def frame_conv3x3_residual(x, weight, bias, residual, res_scale):
 
 
 # ---------------------------------------------------------------------------
-# Flash MFMA attention (K7): HIP forward (saves logsumexp), GEMM-recompute
-# backward (rocBLAS batched matmuls — the "plain library GEMM" path).
+# Flash MFMA attention (K7): HIP forward (saves logsumexp), fused HIP
+# backward, GEMM-recompute backward (rocBLAS batched matmuls) as fallback.
 # ---------------------------------------------------------------------------
 
 # 1/sqrt(d) as attn_fwd.hip forms it (fp32 sqrt, fp32 divide)
@@ -466,8 +466,14 @@ class _Attention(torch.autograd.Function):
         B, L, H, D = q.shape
         Lk = k.shape[1]
         swap = ctx.kv_swap
-        if (D in (16, 32, 64, 128) and L % 128 == 0 and Lk % 128 == 0
-                and os.environ.get("NVS3D_ATTN_BWD", "fused") != "gemm"):
+        mode = os.environ.get("NVS3D_ATTN_BWD")   # "gemm" | "fused" | unset
+        fused = D in (16, 32, 64, 128, 256) and L % 128 == 0 and Lk % 128 == 0
+        if D == 256 and max(L, Lk) > 256 and mode != "fused":
+            # measured: 1.30-1.55x the GEMM path at L=256, 0.76x at L=1024
+            # (the d=256 dkv kernel recomputes S/dP four times); long L
+            # takes the kernel only when asked to
+            fused = False
+        if fused and mode != "gemm":
             # fused flash-style backward (attn_bwd.hip): tile-wise recompute
             # of S/P from q/k/lse — no (B,H,L,L) tensor touches HBM
             doc = do.to(q.dtype).contiguous()
@@ -475,7 +481,7 @@ class _Attention(torch.autograd.Function):
             dq, dk, dv = _OPS.attn_bwd_fused(q, k, v, doc, lse, delta, swap)
             return dq, dk, dv, None
         if swap:
-            # GEMM-recompute fallback shapes (d=256 / short L): materialize
+            # GEMM-recompute fallback shapes (short L): materialize
             # the frame swap, then un-swap the kv grads
             k = swap_frame_pairs(k).contiguous()
             v = swap_frame_pairs(v).contiguous()

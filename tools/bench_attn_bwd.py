@@ -15,10 +15,18 @@ import torch
 sys.path.insert(0, ".")
 
 
-def timeit(fn, warmup=5, iters=20):
+def timeit(fn, warmup=5, window_s=0.3):
+    """ms per call over a window of at least `window_s` seconds (a 20-call
+    window is a few milliseconds at the small shapes: clock and scheduler
+    noise)."""
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(10):
+        fn()
+    torch.cuda.synchronize()
+    iters = max(20, int(window_s / ((time.perf_counter() - t0) / 10)))
     t0 = time.perf_counter()
     for _ in range(iters):
         fn()
@@ -31,7 +39,9 @@ def main():
     shapes = [
         (16, 1024, 4, 128),   # full config res 32 (b16 per-frame batch)
         (32, 1024, 4, 128),
-        (16, 256, 4, 256),    # res 16 (GEMM fallback)
+        (16, 256, 4, 256),    # res 16
+        (32, 256, 4, 256),
+        (16, 1024, 4, 256),   # res 32 of the 256x256 stress config
         (16, 1024, 4, 16),    # small config
     ]
     for B, L, h, d in shapes:
@@ -47,13 +57,29 @@ def main():
             y.backward(do)
             return qq.grad, kk.grad, vv.grad
 
-        os.environ["NVS3D_ATTN_BWD"] = "fused"
-        t_fused = timeit(run_bwd)
-        g_f = run_bwd()
-        os.environ["NVS3D_ATTN_BWD"] = "gemm"
-        t_gemm = timeit(run_bwd)
+        def peak_bytes():
+            """Peak allocated bytes of one forward + backward, above what
+            is allocated before it."""
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            run_bwd()
+            torch.cuda.synchronize()
+            return torch.cuda.max_memory_allocated() - base
+
+        # the two paths alternate, so a drift of the machine shows in both
+        t_f, t_g = [], []
+        for _ in range(3):
+            os.environ["NVS3D_ATTN_BWD"] = "fused"
+            t_f.append(timeit(run_bwd))
+            os.environ["NVS3D_ATTN_BWD"] = "gemm"
+            t_g.append(timeit(run_bwd))
         g_g = run_bwd()
+        mem_gemm = peak_bytes()
         os.environ["NVS3D_ATTN_BWD"] = "fused"
+        g_f = run_bwd()
+        mem_fused = peak_bytes()
+        t_fused, t_gemm = min(t_f), min(t_g)
 
         rel = max(((a - b).abs().max() / (b.abs().max() + 1e-6)).item()
                   for a, b in zip(g_f, g_g))
@@ -63,6 +89,9 @@ def main():
                "fused_ms": round(t_fused, 3), "gemm_ms": round(t_gemm, 3),
                "fused_tflops": round(flops / t_fused / 1e9, 1),
                "speedup": round(t_gemm / t_fused, 2),
+               "fused_ms_runs": [round(t, 3) for t in t_f],
+               "gemm_ms_runs": [round(t, 3) for t in t_g],
+               "fused_peak_bytes": mem_fused, "gemm_peak_bytes": mem_gemm,
                "rel_err_fused_vs_gemm": round(rel, 5)}
         print(json.dumps(rec), flush=True)
 
