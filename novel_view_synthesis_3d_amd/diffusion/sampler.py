@@ -14,10 +14,11 @@ Redesign:
   * logsnr fed at step t is logsnr(t/T) — the level the model saw in
     training. `legacy_logsnr=True` reproduces reference D5 (uses
     logsnr((t+1)/T)),
-  * `solver` / `spacing` / `eta` select a few-step solver (ddim, dpmpp2m)
-    and the timestep spacing from diffusion/solvers.py; the step is then
-    `ops.solver_cfg_step`, which carries the previous x0 prediction. The
-    defaults keep the ancestral path below unchanged.
+  * the post-network part of the step (CFG combine, x0 prediction, clamp,
+    solver update, noise, counter) is one op, `ops.solver_cfg_step`, fed by
+    the tables of diffusion/solvers.py: `solver` / `spacing` / `eta` select
+    ancestral ddpm (the default), ddim or dpmpp2m and the timestep spacing.
+    Both samplers here take their tables and buffers from `solver_state`.
 """
 
 from __future__ import annotations
@@ -26,12 +27,28 @@ from typing import Dict, Optional
 
 import torch
 
-from novel_view_synthesis_3d_amd.diffusion.schedules import (
-    DiffusionSchedule, logsnr_schedule_cosine,
-)
+from novel_view_synthesis_3d_amd.diffusion.schedules import DiffusionSchedule
 from novel_view_synthesis_3d_amd.diffusion.solvers import (
     check_solver_args, device_tables, solver_tables,
 )
+
+
+def solver_state(z: torch.Tensor, schedule: DiffusionSchedule,
+                 num_steps: int, solver: str = "ddpm",
+                 spacing: str = "uniform", eta: float = 0.0,
+                 legacy_logsnr: bool = False) -> Dict:
+    """Tables and static buffers of the solver step for a latent like z:
+    `hist` only for a multistep solver, `noise` (a flag) only when some
+    sigma is nonzero — a deterministic solver issues no randn."""
+    tab64 = solver_tables(schedule, num_steps, solver, spacing=spacing,
+                          eta=eta, legacy_logsnr=legacy_logsnr)
+    return {
+        "tab": device_tables(tab64, z.device),
+        "hist": (torch.zeros_like(z)
+                 if bool((tab64["coef_hist"] != 0).any()) else None),
+        "noise": bool((tab64["sigma"] != 0).any()),
+        "step_scratch": torch.zeros(1, dtype=torch.long, device=z.device),
+    }
 
 
 class DDPMSampler:
@@ -53,64 +70,6 @@ class DDPMSampler:
         self._static = None
 
     # -----------------------------------------------------------------
-    def _step_tables(self, device: torch.device) -> Dict[str, torch.Tensor]:
-        """Per-sampling-step coefficient tables (S,), step index 0 = t=T-1.
-
-        For the full sequence these equal the reference's tables
-        (sampling.py:28-41); for a subsequence they are the generalized
-        DDPM posterior between consecutive kept timesteps.
-        """
-        sched = self.schedule
-        T = sched.timesteps
-        S = self.num_steps
-        # kept timesteps, descending; S=T -> [T-1, ..., 0]
-        ts = torch.linspace(T - 1, 0, S).round().long()
-        abar = sched._tables_f64["alphas_cumprod"]
-        abar_t = abar[ts]
-        abar_prev = torch.cat([abar[ts[1:]], torch.ones(1, dtype=torch.float64)])
-        alpha_eff = abar_t / abar_prev
-        beta_eff = 1.0 - alpha_eff
-        post_var = beta_eff * (1.0 - abar_prev) / (1.0 - abar_t)
-        tab = {
-            "sqrt_recip_abar": torch.sqrt(1.0 / abar_t),
-            "sqrt_recipm1_abar": torch.sqrt(1.0 / abar_t - 1.0),
-            "mean_c1": beta_eff * torch.sqrt(abar_prev) / (1.0 - abar_t),
-            "mean_c2": (1.0 - abar_prev) * torch.sqrt(alpha_eff) / (1.0 - abar_t),
-            "sigma": torch.exp(0.5 * torch.log(post_var.clamp(min=1e-20))),
-        }
-        # noise is zeroed at the final step (t==0) — reference sampling.py:147
-        # (fixing D6: the mask is per-step, not len(z)-shaped)
-        tab["sigma"] = tab["sigma"] * (ts > 0).to(torch.float64)
-        u = (ts + 1 if self.legacy_logsnr else ts).to(torch.float64) / T
-        tab["logsnr"] = torch.tensor(
-            [logsnr_schedule_cosine(float(x)) for x in u], dtype=torch.float64)
-        return {k: v.to(device=device, dtype=torch.float32) for k, v in tab.items()}
-
-    @property
-    def default_solver(self) -> bool:
-        """ddpm on uniform timesteps: the path of `_step_tables` and the
-        ancestral step; anything else goes through diffusion/solvers.py and
-        ops.solver_cfg_step."""
-        return (self.solver == "ddpm" and self.spacing == "uniform"
-                and self.eta == 0.0)
-
-    def _solver_state(self, z: torch.Tensor) -> Dict:
-        """Tables and static buffers of the solver step for a latent like z:
-        `hist` only for a multistep solver, `noise` (a flag) only when some
-        sigma is nonzero — a deterministic solver issues no randn."""
-        tab64 = solver_tables(self.schedule, self.num_steps, self.solver,
-                              spacing=self.spacing, eta=self.eta,
-                              legacy_logsnr=self.legacy_logsnr)
-        step = torch.zeros(1, dtype=torch.long, device=z.device)
-        return {
-            "tab": device_tables(tab64, z.device),
-            "hist": (torch.zeros_like(z)
-                     if bool((tab64["coef_hist"] != 0).any()) else None),
-            "noise": bool((tab64["sigma"] != 0).any()),
-            "step_scratch": torch.zeros_like(step),
-        }
-
-    # -----------------------------------------------------------------
     def _make_cond2(self, cond: Dict[str, torch.Tensor]):
         """Duplicate conditioning along batch for the batched CFG forward."""
         c2 = {k: torch.cat([v, v], dim=0) for k, v in cond.items()
@@ -120,10 +79,12 @@ class DDPMSampler:
                           torch.zeros(B, device=cond["x"].device)])
         return c2, mask
 
-    def _step(self, z: torch.Tensor, idx: torch.Tensor, cond2, mask, tab,
-              pose_cache=None, solver_state=None) -> None:
-        """One in-place step; everything device-side. Ancestral by default;
-        with `solver_state` (and its tables as `tab`) the solver step."""
+    def _step(self, z: torch.Tensor, idx: torch.Tensor, cond2, mask, sst,
+              pose_cache=None) -> None:
+        """One in-place step; everything device-side. `sst` is the
+        `solver_state` of z."""
+        from novel_view_synthesis_3d_amd import ops
+        tab = sst["tab"]
         B = z.shape[0]
         logsnr = tab["logsnr"].index_select(0, idx).expand(2 * B)
         batch = dict(cond2)
@@ -134,29 +95,12 @@ class DDPMSampler:
                 out = self.model(batch, mask, pose_cache=pose_cache)
         else:
             out = self.model(batch, mask, pose_cache=pose_cache)
-        if solver_state is not None:
-            from novel_view_synthesis_3d_amd import ops
-            noise = torch.randn_like(z) if solver_state["noise"] else None
-            ops.solver_cfg_step(
-                z, solver_state["hist"], out, noise, tab["sqrt_recip_abar"],
-                tab["sqrt_recipm1_abar"], tab["coef_z"], tab["coef_x0"],
-                tab["coef_hist"], tab["sigma"], idx, self.w,
-                self.clip_denoised,
-                step_scratch=solver_state["step_scratch"])
-            return
-        out = out.to(torch.float32)
-        eps = (1.0 + self.w) * out[:B] - self.w * out[B:]
-
-        c = {k: tab[k].index_select(0, idx) for k in
-             ("sqrt_recip_abar", "sqrt_recipm1_abar", "mean_c1", "mean_c2",
-              "sigma")}
-        x0 = c["sqrt_recip_abar"] * z - c["sqrt_recipm1_abar"] * eps
-        if self.clip_denoised:
-            x0 = x0.clamp(-1.0, 1.0)
-        mean = c["mean_c1"] * x0 + c["mean_c2"] * z
-        noise = torch.randn_like(z)
-        z.copy_(mean + c["sigma"] * noise)
-        idx.add_(1)
+        noise = torch.randn_like(z) if sst["noise"] else None
+        ops.solver_cfg_step(
+            z, sst["hist"], out, noise, tab["sqrt_recip_abar"],
+            tab["sqrt_recipm1_abar"], tab["coef_z"], tab["coef_x0"],
+            tab["coef_hist"], tab["sigma"], idx, self.w, self.clip_denoised,
+            step_scratch=sst["step_scratch"])
 
     # -----------------------------------------------------------------
     @torch.no_grad()
@@ -176,8 +120,8 @@ class DDPMSampler:
             z = (z_init.clone() if z_init is not None
                  else torch.empty_like(x).normal_(generator=generator))
             cond2, mask = self._make_cond2(cond)
-            sst = None if self.default_solver else self._solver_state(z)
-            tab = self._step_tables(device) if sst is None else sst["tab"]
+            sst = solver_state(z, self.schedule, self.num_steps, self.solver,
+                               self.spacing, self.eta, self.legacy_logsnr)
             idx = torch.zeros(1, dtype=torch.long, device=device)
 
             # Pose conditioning is step-invariant: compute once, outside any
@@ -191,17 +135,16 @@ class DDPMSampler:
                 pose_cache = cp.pose_features(cond2, mask)
 
             if self.use_graph and device.type == "cuda":
-                self._run_graphed(z, idx, cond2, mask, tab, pose_cache, sst)
+                self._run_graphed(z, idx, cond2, mask, sst, pose_cache)
             else:
                 for _ in range(self.num_steps):
-                    self._step(z, idx, cond2, mask, tab, pose_cache, sst)
+                    self._step(z, idx, cond2, mask, sst, pose_cache)
             return z
         finally:
             self.model.train(was_training)
 
     # -----------------------------------------------------------------
-    def _run_graphed(self, z, idx, cond2, mask, tab, pose_cache,
-                     solver_state=None) -> None:
+    def _run_graphed(self, z, idx, cond2, mask, sst, pose_cache) -> None:
         """Capture one sampler step as a hipGraph and replay it num_steps
         times. Per-step state (z, idx) lives in the captured buffers; RNG is
         graph-safe (torch captures the philox offset)."""
@@ -213,8 +156,7 @@ class DDPMSampler:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):  # warmup, required before capture
             for _ in range(n_warm):
-                self._step(z, idx, cond2, mask, tab, pose_cache,
-                           solver_state)
+                self._step(z, idx, cond2, mask, sst, pose_cache)
         torch.cuda.current_stream().wait_stream(s)
         done_warmup = int(idx.item())
         if self.num_steps - done_warmup <= 0:
@@ -224,7 +166,7 @@ class DDPMSampler:
         with torch.cuda.graph(graph):
             # capture RECORDS the step without executing it; z/idx advance
             # only on replay
-            self._step(z, idx, cond2, mask, tab, pose_cache, solver_state)
+            self._step(z, idx, cond2, mask, sst, pose_cache)
         for _ in range(self.num_steps - done_warmup):
             graph.replay()
 
@@ -288,7 +230,7 @@ class StochasticConditioningSampler:
         return contextlib.nullcontext()
 
     def _step(self, st) -> None:
-        """One in-place ancestral step on st["z"]; everything device-side."""
+        """One in-place step on st["z"]; everything device-side."""
         from novel_view_synthesis_3d_amd import ops
         z, tab = st["z"], st["tab"]
         B = z.shape[0]
@@ -297,23 +239,13 @@ class StochasticConditioningSampler:
                      0, st["step"]).expand(2 * B)}
         with self._ctx(z.device):
             out = self.model(batch, st["mask"], pose_cache=st["cache"])
-        if st["solver_step"]:
-            noise = torch.randn_like(z) if st["draw_noise"] else None
-            ops.solver_cfg_step(
-                z, st["hist"], out, noise, tab["sqrt_recip_abar"],
-                tab["sqrt_recipm1_abar"], tab["coef_z"], tab["coef_x0"],
-                tab["coef_hist"], tab["sigma"], st["step"], st["w"],
-                st["clip"], st["noise_scale"], u=st["u"], k=st["k"],
-                bank_img=st["bank_img"], x=st["x2"],
-                step_scratch=st["step_scratch"])
-            return
-        noise = torch.randn_like(z)
-        ops.ddpm_cfg_step(z, out, noise, tab["sqrt_recip_abar"],
-                          tab["sqrt_recipm1_abar"], tab["mean_c1"],
-                          tab["mean_c2"], tab["sigma"], st["step"], st["u"],
-                          st["k"], st["bank_img"], st["x2"], st["w"],
-                          st["clip"], st["noise_scale"],
-                          step_scratch=st["step_scratch"])
+        noise = torch.randn_like(z) if st["noise"] else None
+        ops.solver_cfg_step(
+            z, st["hist"], out, noise, tab["sqrt_recip_abar"],
+            tab["sqrt_recipm1_abar"], tab["coef_z"], tab["coef_x0"],
+            tab["coef_hist"], tab["sigma"], st["step"], st["w"], st["clip"],
+            st["noise_scale"], u=st["u"], k=st["k"], bank_img=st["bank_img"],
+            x=st["x2"], step_scratch=st["step_scratch"])
 
     def _frame_features(self, st, R, t, frame):
         cp = self.model.ConditioningProcessor_0
@@ -424,9 +356,6 @@ class StochasticConditioningSampler:
                 # ring bank: the input view would be evicted
                 raise ValueError("stochastic=False needs the input view to "
                                  "stay in the bank (max_bank too small)")
-            helper = DDPMSampler(model, self.schedule, num_steps=S,
-                                 legacy_logsnr=self.legacy_logsnr,
-                                 solver=solver, spacing=spacing, eta=eta)
             cfg = model.cfg
             E, L = cfg.emb_ch, cfg.num_resolutions
             act = (torch.bfloat16 if device.type == "cuda" and self.autocast
@@ -450,22 +379,18 @@ class StochasticConditioningSampler:
                 "S": S, "Kcap": Kcap, "count": 0, "graph": None,
                 "w": float(guidance_weight), "clip": bool(clip_denoised),
                 "noise_scale": float(noise_scale),
-                "tab": helper._step_tables(device), "K": K,
-                "z": torch.zeros(B, H, W, 3, **f32),
+                "K": K, "z": torch.zeros(B, H, W, 3, **f32),
                 "x2": torch.zeros(2 * B, H, W, 3, **f32),
                 "mask": torch.cat([torch.ones(B, device=device),
                                    torch.zeros(B, device=device)]),
                 "bank_img": torch.zeros(Kcap, B, H, W, 3, **f32),
-                "step": step, "step_scratch": torch.zeros_like(step),
-                "k": k, "u": u, "cache": cache,
-                "solver_step": False, "hist": None, "draw_noise": True,
+                "step": step, "k": k, "u": u, "cache": cache,
             }
-            if not helper.default_solver:
-                # hist is static like z: captured in the graph and never
-                # reset per view (coef_hist[0] = 0 keeps it out of step 0)
-                sst = helper._solver_state(st["z"])
-                st.update(solver_step=True, tab=sst["tab"],
-                          hist=sst["hist"], draw_noise=sst["noise"])
+            # tab, hist, noise, step_scratch. hist is static like z: captured
+            # in the graph and never reset per view (coef_hist[0] = 0 keeps
+            # it out of step 0)
+            st.update(solver_state(st["z"], self.schedule, S, solver, spacing,
+                                   float(eta), self.legacy_logsnr))
             # the null source feature is camera-independent: computed once
             _, null0 = self._frame_features(st, R0, t0, 0)
             cache.null = [nf.contiguous() for nf in null0]

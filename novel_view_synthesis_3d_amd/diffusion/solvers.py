@@ -12,8 +12,9 @@ ap = abar of the next kept timestep (1 after the last); alpha = sqrt(.),
 sigma_* = sqrt(1 - .); lambda = log(alpha / sigma_*) (half the log-SNR);
 h = lambda_next - lambda_t.
 
-  ddpm     ancestral sampling: the generalized posterior between consecutive
-           kept timesteps (the tables of DDPMSampler._step_tables).
+  ddpm     ancestral sampling, the samplers' default: the generalized DDPM
+           posterior between consecutive kept timesteps. Over the full
+           sequence (S = T) these are the classic posterior tables.
   ddim     Song et al. 2021, eq. 12; eta = 0 is deterministic and equals
            first-order DPM-Solver++, eta = 1 is ddpm.
   dpmpp2m  DPM-Solver++(2M), Lu et al. 2022, algorithm 2: second-order
@@ -115,7 +116,9 @@ def solver_tables(schedule: DiffusionSchedule, num_steps: int, solver: str,
     a_n, s_n = torch.sqrt(ap), torch.sqrt(1.0 - ap)
 
     if solver == "ddpm":
-        # the expressions of DDPMSampler._step_tables, term for term
+        # posterior q(z_prev | z_t, x0) between kept timesteps: mean
+        # coef_x0 x0 + coef_z z, variance floored at 1e-20; the noise is
+        # zeroed at the final step (t == 0)
         alpha_eff = at / ap
         beta_eff = 1.0 - alpha_eff
         post_var = beta_eff * (1.0 - ap) / (1.0 - at)

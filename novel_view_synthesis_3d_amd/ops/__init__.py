@@ -166,20 +166,6 @@ def cond_emb_select(logsnr_emb, bank, null_feat, tgt_feat, u, step, k):
                                step, k)
 
 
-def ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma, step, u, k,
-                  bank_img, x, w: float, clip: bool,
-                  noise_scale: float = 1.0, step_scratch=None) -> None:
-    """CFG combine + ancestral step in place on z; advances `step` and
-    writes the next step's model input x from the image bank.
-    `step_scratch` is a one-element int64 work slot of the HIP kernels."""
-    if _use_hip(z, "ddpm_cfg_step"):
-        return _HIP_MOD.ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma,
-                                      step, u, k, bank_img, x, w, clip,
-                                      noise_scale, step_scratch)
-    return ref.ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma, step, u,
-                             k, bank_img, x, w, clip, noise_scale)
-
-
 def solver_cfg_step(z, hist, out, noise, c_a, c_b, coef_z, coef_x0, coef_hist,
                     sigma, step, w: float, clip: bool,
                     noise_scale: float = 1.0, *, u=None, k=None,
@@ -187,7 +173,8 @@ def solver_cfg_step(z, hist, out, noise, c_a, c_b, coef_z, coef_x0, coef_hist,
     """CFG combine + one step of a solver of diffusion/solvers.py in place on
     z; hist (or None) carries the previous step's x0, noise may be None.
     Advances `step`; with u, k, bank_img and x also writes the next step's
-    model input x from the image bank, as ddpm_cfg_step does."""
+    model input x from the image bank. `step_scratch` is a one-element int64
+    work slot of the HIP kernels."""
     if _use_hip(z, "solver_cfg_step"):
         return _HIP_MOD.solver_cfg_step(
             z, hist, out, noise, c_a, c_b, coef_z, coef_x0, coef_hist, sigma,

@@ -63,13 +63,6 @@ torch::Tensor cond_emb_select(torch::Tensor lemb, torch::Tensor bank,
                               torch::Tensor nullf, torch::Tensor tgt,
                               torch::Tensor u, torch::Tensor step,
                               torch::Tensor kvalid);
-void ddpm_cfg_step(torch::Tensor z, torch::Tensor out, torch::Tensor noise,
-                   torch::Tensor t_ca, torch::Tensor t_cb, torch::Tensor t_c1,
-                   torch::Tensor t_c2, torch::Tensor t_sigma,
-                   torch::Tensor step, torch::Tensor step_next,
-                   torch::Tensor u, torch::Tensor kvalid,
-                   torch::Tensor bank_img, torch::Tensor x, double w,
-                   bool clip, double noise_scale);
 void solver_cfg_step(torch::Tensor z, c10::optional<torch::Tensor> hist,
                      torch::Tensor out, c10::optional<torch::Tensor> noise,
                      torch::Tensor t_ca, torch::Tensor t_cb,
@@ -129,11 +122,6 @@ TORCH_LIBRARY(nvs3d, m) {
   m.def("add_scale(Tensor a, Tensor b, float scale) -> Tensor");
   m.def("cond_emb_select(Tensor lemb, Tensor bank, Tensor nullf, Tensor tgt, "
         "Tensor u, Tensor step, Tensor kvalid) -> Tensor");
-  m.def("ddpm_cfg_step(Tensor(a!) z, Tensor out, Tensor noise, Tensor t_ca, "
-        "Tensor t_cb, Tensor t_c1, Tensor t_c2, Tensor t_sigma, "
-        "Tensor(b!) step, Tensor(c!) step_next, Tensor u, Tensor kvalid, "
-        "Tensor bank_img, Tensor(d!) x, float w, bool clip, "
-        "float noise_scale) -> ()");
   m.def("solver_cfg_step(Tensor(a!) z, Tensor(b!)? hist, Tensor out, "
         "Tensor? noise, Tensor t_ca, Tensor t_cb, Tensor t_cz, Tensor t_cx, "
         "Tensor t_ch, Tensor t_sigma, Tensor(c!) step, Tensor(d!) step_next, "
@@ -167,7 +155,6 @@ TORCH_LIBRARY_IMPL(nvs3d, CUDA, m) {
   m.impl("pool2x_bwd", pool2x_bwd);
   m.impl("add_scale", add_scale);
   m.impl("cond_emb_select", cond_emb_select);
-  m.impl("ddpm_cfg_step", ddpm_cfg_step);
   m.impl("solver_cfg_step", solver_cfg_step);
   m.impl("image_metrics", image_metrics);
 }

@@ -6,14 +6,14 @@
 //    unconditional half is the (view-independent) null feature and frame 1 is
 //    the target-frame feature. Replaces the eager add + silu passes of
 //    XUNet.forward's emb_at at the same memory traffic.
-//  * ddpm_cfg_step: CFG combine + x0 prediction (+clamp) + posterior mean +
-//    noise, in place on z, coefficients read from the device step tables at
-//    the device step counter; a second small kernel writes the next step's
-//    model input x from the image bank and publishes the advanced counter.
-//  * solver_cfg_step: the same step for any solver of diffusion/solvers.py
-//    (ddpm, ddim, dpmpp2m): z' = coef_z z + coef_x0 x0 + coef_hist x0_prev
+//  * solver_cfg_step: the reverse step of every solver of
+//    diffusion/solvers.py (ddpm, ddim, dpmpp2m), in place on z: CFG combine +
+//    x0 prediction (+clamp) + z' = coef_z z + coef_x0 x0 + coef_hist x0_prev
 //    + sigma noise, with one optional history buffer (the previous step's x0)
-//    and optional noise; the same gather kernel follows when there is a bank.
+//    and optional noise, coefficients read from the device step tables at
+//    the device step counter. A second small kernel publishes the advanced
+//    counter; with an image bank it first writes the next step's model input
+//    x from the bank.
 //
 // Index rule (shared with ops/reference.py stochastic_index):
 //   idx[s,b] = min(floor(u[s,b] * k), k-1) in fp32, s = device step counter,
@@ -90,63 +90,6 @@ __global__ void cond_emb_select_kernel(
   }
 }
 
-__device__ __forceinline__ float ddpm_elem(float z, float oc, float ou,
-                                           float nz, float w, float ca,
-                                           float cb, float c1, float c2,
-                                           float sg, bool clip) {
-  const float eps = (1.0f + w) * oc - w * ou;
-  float x0 = ca * z - cb * eps;
-  if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-  return c1 * x0 + c2 * z + sg * nz;
-}
-
-// z (n) <- posterior sample; out holds the conditional half at [0,n) and the
-// unconditional half at [n,2n). 4-element packs (16 B of fp32) + scalar
-// tail. ALIGNED_U: n % 4 == 0, so the unconditional half is pack-aligned;
-// otherwise its loads are scalar.
-template <typename TO, bool ALIGNED_U>
-__global__ void ddpm_cfg_step_kernel(
-    float* __restrict__ z, const TO* __restrict__ out,
-    const float* __restrict__ noise, const float* __restrict__ t_ca,
-    const float* __restrict__ t_cb, const float* __restrict__ t_c1,
-    const float* __restrict__ t_c2, const float* __restrict__ t_sigma,
-    const long* __restrict__ step, long* __restrict__ step_next,
-    long n, int S, float w, float noise_scale, int clip) {
-  const long s_raw = step[0];
-  const long s = clampl(s_raw, 0, S - 1);
-  const float ca = t_ca[s], cb = t_cb[s], c1 = t_c1[s], c2 = t_c2[s];
-  const float sg = noise_scale * t_sigma[s];
-  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long gstride = (long)gridDim.x * blockDim.x;
-  const long npack = n / 4;
-  for (long i = tid; i < npack; i += gstride) {
-    Pack<float, 4> vz = pload<float, 4>(z + i * 4);
-    Pack<float, 4> vn = pload<float, 4>(noise + i * 4);
-    Pack<TO, 4> vc = pload<TO, 4>(out + i * 4);
-    Pack<TO, 4> vu;
-    if (ALIGNED_U) {
-      vu = pload<TO, 4>(out + n + i * 4);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) vu.v[j] = out[n + i * 4 + j];
-    }
-    Pack<float, 4> o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      o.v[j] = ddpm_elem(vz.v[j], to_f32(vc.v[j]), to_f32(vu.v[j]), vn.v[j],
-                         w, ca, cb, c1, c2, sg, clip != 0);
-    pstore<float, 4>(z + i * 4, o);
-  }
-  // scalar tail: n % 4 trailing elements
-  const long i = npack * 4 + tid;
-  if (i < n)
-    z[i] = ddpm_elem(z[i], to_f32(out[i]), to_f32(out[n + i]), noise[i], w,
-                     ca, cb, c1, c2, sg, clip != 0);
-  // The advanced counter goes to a shadow slot: other blocks of this launch
-  // may still be reading step[0]. The gather kernel publishes it.
-  if (tid == 0) step_next[0] = s_raw + 1;
-}
-
 // One step of a solver of diffusion/solvers.py on one element:
 //   x0 = ca z - cb eps (clamped);  z' = cz z + cx x0 [+ ch h] [+ sg nz].
 // Explicit fma chain: the rounding does not depend on the contraction mode.
@@ -169,9 +112,11 @@ __device__ __forceinline__ float solver_elem(float z, float oc, float ou,
   return r;
 }
 
-// z (n) <- solver step, hist (n) <- x0; layout of `out`, packs, tail and
-// ALIGNED_U as in ddpm_cfg_step_kernel. hist and noise may be null. hist is
-// READ only when the step's coef_hist is nonzero (0 * NaN would reach z
+// z (n) <- solver step, hist (n) <- x0; out holds the conditional half at
+// [0,n) and the unconditional half at [n,2n). 4-element packs (16 B of fp32)
+// + scalar tail. ALIGNED_U: n % 4 == 0, so the unconditional half is
+// pack-aligned; otherwise its loads are scalar. hist and noise may be null.
+// hist is READ only when the step's coef_hist is nonzero (0 * NaN would reach z
 // otherwise) and written whenever it is given; noise is read only when it is
 // given. All three conditions are uniform over the launch.
 template <typename TO, bool ALIGNED_U>
@@ -228,8 +173,8 @@ __global__ void solver_cfg_step_kernel(
                        x0);
     if (wr_hist) hist[i] = x0;
   }
-  // shadow slot, as in ddpm_cfg_step_kernel: other blocks of this launch
-  // may still be reading step[0]
+  // The advanced counter goes to a shadow slot: other blocks of this launch
+  // may still be reading step[0]. The kernel that follows publishes it.
   if (tid == 0) step_next[0] = s_raw + 1;
 }
 
@@ -350,82 +295,6 @@ torch::Tensor cond_emb_select(torch::Tensor lemb, torch::Tensor bank,
     else launch((float*)nullptr, std::integral_constant<int, 1>{});
   }
   return out;
-}
-
-void ddpm_cfg_step(torch::Tensor z, torch::Tensor out, torch::Tensor noise,
-                   torch::Tensor t_ca, torch::Tensor t_cb, torch::Tensor t_c1,
-                   torch::Tensor t_c2, torch::Tensor t_sigma,
-                   torch::Tensor step, torch::Tensor step_next,
-                   torch::Tensor u, torch::Tensor kvalid,
-                   torch::Tensor bank_img, torch::Tensor x, double w,
-                   bool clip, double noise_scale) {
-  TORCH_CHECK(z.is_cuda() && z.is_contiguous()
-              && z.scalar_type() == torch::kFloat && z.dim() == 4);
-  TORCH_CHECK(noise.is_contiguous() && noise.scalar_type() == torch::kFloat
-              && noise.numel() == z.numel());
-  TORCH_CHECK(out.is_contiguous() && out.numel() == 2 * z.numel()
-              && (out.scalar_type() == torch::kBFloat16
-                  || out.scalar_type() == torch::kFloat));
-  const int B = z.size(0);
-  const long n = z.numel();
-  const long m = n / B;
-  check_index_inputs(u, step, kvalid, B);
-  const int S = u.size(0);
-  for (const auto* t : {&t_ca, &t_cb, &t_c1, &t_c2, &t_sigma})
-    TORCH_CHECK(t->is_cuda() && t->is_contiguous()
-                && t->scalar_type() == torch::kFloat && t->numel() == S,
-                "step tables must be fp32 (S,) matching u's S");
-  TORCH_CHECK(step_next.is_cuda() && step_next.scalar_type() == torch::kLong
-              && step_next.numel() == 1
-              && step_next.data_ptr() != step.data_ptr());
-  TORCH_CHECK(bank_img.is_cuda() && bank_img.is_contiguous()
-              && bank_img.scalar_type() == torch::kFloat
-              && bank_img.dim() == 5 && bank_img.size(0) >= 1
-              && bank_img.size(1) == B && bank_img.numel()
-                 == bank_img.size(0) * n);
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous()
-              && x.scalar_type() == torch::kFloat && x.numel() == 2 * n);
-  const int Kcap = bank_img.size(0);
-  TORCH_CHECK(aligned16(z) && aligned16(noise) && aligned16(out),
-              "ddpm_cfg_step: z/noise/out must be 16-byte aligned");
-
-  auto stream = at::hip::getCurrentHIPStream();
-  const int grid = grid_for((n + 3) / 4);
-  auto launch = [&](auto* tag, auto atag) {
-    using TO = std::remove_pointer_t<decltype(tag)>;
-    constexpr bool AL = decltype(atag)::value;
-    hipLaunchKernelGGL((ddpm_cfg_step_kernel<TO, AL>), dim3(grid), dim3(256),
-        0, stream, z.data_ptr<float>(),
-        reinterpret_cast<const TO*>(out.data_ptr()), noise.data_ptr<float>(),
-        t_ca.data_ptr<float>(), t_cb.data_ptr<float>(),
-        t_c1.data_ptr<float>(), t_c2.data_ptr<float>(),
-        t_sigma.data_ptr<float>(),
-        reinterpret_cast<const long*>(step.data_ptr()),
-        reinterpret_cast<long*>(step_next.data_ptr()), n, S, (float)w,
-        (float)noise_scale, clip ? 1 : 0);
-  };
-  const bool al = n % 4 == 0;
-  if (out.scalar_type() == torch::kBFloat16) {
-    if (al) launch((bf16*)nullptr, std::true_type{});
-    else launch((bf16*)nullptr, std::false_type{});
-  } else {
-    if (al) launch((float*)nullptr, std::true_type{});
-    else launch((float*)nullptr, std::false_type{});
-  }
-
-  const bool vec = m % 4 == 0 && aligned16(bank_img) && aligned16(x);
-  auto gather = [&](auto vtag) {
-    constexpr int V = decltype(vtag)::value;
-    const long total = n / V;
-    hipLaunchKernelGGL((next_x_gather_kernel<V>), dim3(grid_for(total)),
-        dim3(256), 0, stream, bank_img.data_ptr<float>(),
-        x.data_ptr<float>(), u.data_ptr<float>(),
-        reinterpret_cast<const long*>(step_next.data_ptr()),
-        reinterpret_cast<const long*>(kvalid.data_ptr()),
-        reinterpret_cast<long*>(step.data_ptr()), total, B, m, S, Kcap);
-  };
-  if (vec) gather(std::integral_constant<int, 4>{});
-  else gather(std::integral_constant<int, 1>{});
 }
 
 // Solver step (ddpm / ddim / dpmpp2m tables). hist and noise are optional;

@@ -644,7 +644,7 @@ def residual_scale_add(h, h_in):
 # Stochastic-conditioning sampler step (sampler_step.hip); inference only
 # ---------------------------------------------------------------------------
 
-HAS |= {"cond_emb_select", "ddpm_cfg_step"}
+HAS |= {"cond_emb_select", "solver_cfg_step"}
 
 
 def cond_emb_select(logsnr_emb, bank, null_feat, tgt_feat, u, step, k):
@@ -655,29 +655,15 @@ def cond_emb_select(logsnr_emb, bank, null_feat, tgt_feat, u, step, k):
             tgt_feat.to(dt).contiguous(), u, step, k)
 
 
-def ddpm_cfg_step(z, out, noise, c_a, c_b, c1, c2, sigma, step, u, k,
-                  bank_img, x, w, clip, noise_scale=1.0,
-                  step_scratch=None) -> None:
-    """`step_scratch`: one-element int64 slot the step kernel writes the
-    advanced counter to (its other blocks may still be reading the live
-    one); the gather kernel publishes it. A caller that steps repeatedly
-    (or under graph capture) keeps one next to `step`."""
-    if step_scratch is None:
-        step_scratch = torch.empty_like(step)
-    with torch.no_grad():
-        _OPS.ddpm_cfg_step(z, out.contiguous(), noise, c_a, c_b, c1, c2,
-                           sigma, step, step_scratch, u, k, bank_img, x,
-                           float(w), bool(clip), float(noise_scale))
-
-
-HAS |= {"solver_cfg_step"}
-
-
 def solver_cfg_step(z, hist, out, noise, c_a, c_b, coef_z, coef_x0, coef_hist,
                     sigma, step, w, clip, noise_scale=1.0, *, u=None, k=None,
                     bank_img=None, x=None, step_scratch=None) -> None:
     """hist and noise may be None; u, k, bank_img, x come together or not at
-    all. `step_scratch` as in ddpm_cfg_step."""
+    all. `step_scratch`: one-element int64 slot the step kernel writes the
+    advanced counter to (its other blocks may still be reading the live
+    one); the kernel that follows (the gather, or the one-thread publish
+    without a bank) publishes it. A caller that steps repeatedly (or under
+    graph capture) keeps one next to `step`."""
     if step_scratch is None:
         step_scratch = torch.empty_like(step)
     with torch.no_grad():

@@ -219,39 +219,6 @@ def cond_emb_select(logsnr_emb: torch.Tensor, bank: torch.Tensor,
     return F.silu(e).to(bank.dtype)
 
 
-def ddpm_cfg_step(z: torch.Tensor, out: torch.Tensor, noise: torch.Tensor,
-                  c_a: torch.Tensor, c_b: torch.Tensor, c1: torch.Tensor,
-                  c2: torch.Tensor, sigma: torch.Tensor, step: torch.Tensor,
-                  u: torch.Tensor, k: torch.Tensor, bank_img: torch.Tensor,
-                  x: torch.Tensor, w: float, clip: bool,
-                  noise_scale: float = 1.0) -> None:
-    """One post-network ancestral step, in place on z, step and x.
-
-    eps = (1+w) out[:B] - w out[B:];  x0 = c_a z - c_b eps (clamped to
-    [-1,1] if clip);  z <- c1 x0 + c2 z + noise_scale sigma noise, with the
-    coefficients taken from the (S,) tables at `step`. Then step += 1 and,
-    while steps remain, x (2B,...) <- bank_img[idx_next[b], b] for both CFG
-    halves under the index rule at the advanced step."""
-    B = z.shape[0]
-    S = u.shape[0]
-    s = step.reshape(1)
-    o = out.to(torch.float32)
-    eps = (1.0 + w) * o[:B] - w * o[B:]
-    x0 = c_a.index_select(0, s) * z - c_b.index_select(0, s) * eps
-    if clip:
-        x0 = x0.clamp(-1.0, 1.0)
-    mean = c1.index_select(0, s) * x0 + c2.index_select(0, s) * z
-    z.copy_(mean + (noise_scale * sigma.index_select(0, s)) * noise)
-    step.add_(1)
-    # no data-dependent host branch: past the last step the clamped row is
-    # gathered and then discarded by the where()
-    s1 = step.reshape(1).clamp(max=S - 1)
-    idx = stochastic_index(u.index_select(0, s1)[0], k)
-    nxt = bank_img[idx, torch.arange(B, device=z.device)]
-    live = (step.reshape(()) < S)
-    x.copy_(torch.where(live, torch.cat([nxt, nxt], dim=0), x))
-
-
 def solver_cfg_step(z: torch.Tensor, hist: Optional[torch.Tensor],
                     out: torch.Tensor, noise: Optional[torch.Tensor],
                     c_a: torch.Tensor, c_b: torch.Tensor,
@@ -269,8 +236,9 @@ def solver_cfg_step(z: torch.Tensor, hist: Optional[torch.Tensor],
     from the (S,) tables at `step`. hist enters only where coef_hist is
     nonzero, so whatever it holds at the first step of a view (stale values,
     NaN) never reaches z; hist=None is a first-order solver, noise=None a
-    deterministic one. With u, k, bank_img and x the next step's x is
-    gathered as in ddpm_cfg_step."""
+    deterministic one. With u, k, bank_img and x, while steps remain,
+    x (2B,...) <- bank_img[idx_next[b], b] for both CFG halves under the
+    index rule at the advanced step."""
     B = z.shape[0]
     S = coef_z.shape[0]
     s = step.reshape(1)
@@ -291,6 +259,8 @@ def solver_cfg_step(z: torch.Tensor, hist: Optional[torch.Tensor],
     step.add_(1)
     if bank_img is None:
         return
+    # no data-dependent host branch: past the last step the clamped row is
+    # gathered and then discarded by the where()
     s1 = step.reshape(1).clamp(max=S - 1)
     idx = stochastic_index(u.index_select(0, s1)[0], k)
     nxt = bank_img[idx, torch.arange(B, device=z.device)]

@@ -40,23 +40,29 @@ COEFS = ("sqrt_recip_abar", "sqrt_recipm1_abar", "coef_z", "coef_x0",
 # 1-4: tables and spacing
 # ---------------------------------------------------------------------------
 
+@pytest.fixture(scope="module")
+def golden_tables():
+    """fp32 tables dumped from the ancestral sampler's own table builder
+    before `solver_tables` became the only definition."""
+    import numpy as np
+    with np.load(os.path.join(ROOT, "tests", "golden",
+                              "ddpm_step_tables.npz")) as f:
+        return {k: torch.from_numpy(f[k]) for k in f.files}
+
+
 @pytest.mark.parametrize("S", [1, 7, 256, 1000])
-def test_ddpm_tables_equal_step_tables(S):
+def test_ddpm_tables_equal_step_tables(S, golden_tables):
     tab = solver_tables(SCHED, S, "ddpm")
-    old = DDPMSampler(None, SCHED, num_steps=S)._step_tables(
-        torch.device("cpu"))
-    for new, name in (("coef_x0", "mean_c1"), ("coef_z", "mean_c2"),
-                      ("sigma", "sigma"), ("logsnr", "logsnr"),
-                      ("sqrt_recip_abar", "sqrt_recip_abar"),
-                      ("sqrt_recipm1_abar", "sqrt_recipm1_abar")):
-        assert tab[new].dtype == torch.float64 and tab[new].shape == (S,)
-        assert torch.equal(tab[new].to(torch.float32), old[name]), new
+    for name in ("coef_x0", "coef_z", "sigma", "logsnr", "sqrt_recip_abar",
+                 "sqrt_recipm1_abar"):
+        assert tab[name].dtype == torch.float64 and tab[name].shape == (S,)
+        assert torch.equal(tab[name].to(torch.float32),
+                           golden_tables[f"s{S}_{name}"]), name
     assert not tab["coef_hist"].any()
     assert torch.equal(tab["ts"], torch.linspace(T - 1, 0, S).round().long())
     legacy = solver_tables(SCHED, S, "ddpm", legacy_logsnr=True)
-    old = DDPMSampler(None, SCHED, num_steps=S, legacy_logsnr=True
-                      )._step_tables(torch.device("cpu"))
-    assert torch.equal(legacy["logsnr"].to(torch.float32), old["logsnr"])
+    assert torch.equal(legacy["logsnr"].to(torch.float32),
+                       golden_tables[f"s{S}_logsnr_legacy"])
 
 
 @pytest.mark.parametrize("S", [1, 7, 256, 1000])
@@ -284,6 +290,56 @@ def test_oracle_op_matches_float64_restatement(solver, eta):
                                 assert torch.equal(x, torch.cat([nxt, nxt]))
                             else:
                                 assert (x == -7.0).all()
+
+
+@pytest.mark.parametrize("out_dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("shape", [(2, 4, 4, 3), (1, 5, 5, 3)])
+def test_ddpm_row_is_the_ancestral_step_bitwise(shape, out_dtype):
+    """The ddpm row with hist=None against the ancestral step written out
+    (c1 x0 + c2 z, then the noise term): equal bits on the CPU, since the
+    oracle differs only in the order of one fp32 add."""
+    S, B, Kcap, k = 8, shape[0], 3, 2
+    tab64 = solver_tables(SCHED, S, "ddpm")
+    tab = {n: tab64[n].to(torch.float32) for n in COEFS}
+    g = torch.Generator().manual_seed(23)
+    u = torch.rand(S, B, generator=g)
+    bank = torch.randn(Kcap, *shape, generator=g)
+    bank[k:] = float("nan")
+    rows = torch.arange(B)
+    for s in (0, 4, 7):
+        for clip in (True, False):
+            for w in (0.0, 3.0):
+                for noise_scale in (1.0, 0.5):
+                    for with_bank in (True, False):
+                        z0 = torch.randn(*shape, generator=g)
+                        out = torch.randn(2 * B, *shape[1:],
+                                          generator=g).to(out_dtype)
+                        noise = torch.randn(*shape, generator=g)
+                        z = z0.clone()
+                        x = torch.full((2 * B, *shape[1:]), -7.0)
+                        step = torch.tensor([s])
+                        kw = (dict(u=u, k=torch.tensor([k]), bank_img=bank,
+                                   x=x) if with_bank else {})
+                        ref.solver_cfg_step(
+                            z, None, out, noise, *(tab[n] for n in COEFS),
+                            step, w, clip, noise_scale, **kw)
+                        o = out.to(torch.float32)
+                        eps = (1.0 + w) * o[:B] - w * o[B:]
+                        x0 = (tab["sqrt_recip_abar"][s] * z0
+                              - tab["sqrt_recipm1_abar"][s] * eps)
+                        if clip:
+                            x0 = x0.clamp(-1.0, 1.0)
+                        c1, c2 = tab["coef_x0"][s], tab["coef_z"][s]
+                        want = (c1 * x0 + c2 * z0
+                                + (noise_scale * tab["sigma"][s]) * noise)
+                        assert torch.equal(z, want)
+                        assert int(step) == s + 1
+                        if with_bank and s + 1 < S:
+                            idx = ref.stochastic_index(u[s + 1], k)
+                            nxt = bank[idx, rows]
+                            assert torch.equal(x, torch.cat([nxt, nxt]))
+                        else:
+                            assert (x == -7.0).all()
 
 
 # ---------------------------------------------------------------------------

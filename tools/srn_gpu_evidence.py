@@ -72,7 +72,9 @@ def throughput_srn():
 def overfit_and_sample():
     from novel_view_synthesis_3d_amd.config import TrainConfig, XUNetConfig
     from novel_view_synthesis_3d_amd.data.srn import SceneClassDataset
-    from novel_view_synthesis_3d_amd.diffusion.sampler import DDPMSampler
+    from novel_view_synthesis_3d_amd.diffusion.sampler import (
+        DDPMSampler, solver_state,
+    )
     from novel_view_synthesis_3d_amd.engine.trainer import Trainer
     from PIL import Image
 
@@ -133,15 +135,15 @@ def overfit_and_sample():
     # (indices 650..999 = t 349..0); no guidance (w=0)
     sam2 = DDPMSampler(model, num_steps=1000, guidance_weight=0.0,
                        use_graph=False)
-    tab = sam2._step_tables(torch.device("cuda"))
-    tab = {k: v[1000 - t_noise:] for k, v in tab.items()}
+    sst = solver_state(z, sched, 1000)
+    sst["tab"] = {k: v[1000 - t_noise:] for k, v in sst["tab"].items()}
     cond2, mask = sam2._make_cond2(cond)
     idx = torch.zeros(1, dtype=torch.long, device="cuda")
     cp = model.ConditioningProcessor_0
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
         pose_cache = cp.pose_features(cond2, mask)
         for _ in range(t_noise):
-            sam2._step(z, idx, cond2, mask, tab, pose_cache)
+            sam2._step(z, idx, cond2, mask, sst, pose_cache)
     save_grid(z, "evidence_denoised_from_t350.png")
     err = (z - gt).abs().mean().item()
     rec = {"evidence": "denoise_check", "t_noise": t_noise,
