@@ -36,6 +36,10 @@ torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w,
                           c10::optional<torch::Tensor> bias,
                           c10::optional<torch::Tensor> residual,
                           double out_scale);
+torch::Tensor conv3x3_halo_fwd(torch::Tensor x, torch::Tensor w,
+                               c10::optional<torch::Tensor> bias,
+                               c10::optional<torch::Tensor> residual,
+                               double out_scale);
 std::vector<torch::Tensor> conv3x3_wgrad(torch::Tensor x, torch::Tensor dy,
                                          bool with_bias);
 std::vector<torch::Tensor> linear_wgrad(torch::Tensor dy, torch::Tensor x,
@@ -106,6 +110,7 @@ TORCH_LIBRARY(nvs3d, m) {
   m.def("grad_norm_finalize(Tensor partials, Tensor(a!) ctrl, "
         "float max_norm) -> ()");
   m.def("conv3x3_fwd(Tensor x, Tensor w, Tensor? bias, Tensor? residual, float out_scale) -> Tensor");
+  m.def("conv3x3_halo_fwd(Tensor x, Tensor w, Tensor? bias, Tensor? residual, float out_scale) -> Tensor");
   m.def("conv3x3_wgrad(Tensor x, Tensor dy, bool with_bias) -> Tensor[]");
   m.def("linear_wgrad(Tensor dy, Tensor x, bool with_bias) -> Tensor[]");
   m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool kv_swap=False) -> Tensor[]");
@@ -141,6 +146,7 @@ TORCH_LIBRARY_IMPL(nvs3d, CUDA, m) {
   m.impl("grad_sqnorm", grad_sqnorm);
   m.impl("grad_norm_finalize", grad_norm_finalize);
   m.impl("conv3x3_fwd", conv3x3_fwd);
+  m.impl("conv3x3_halo_fwd", conv3x3_halo_fwd);
   m.impl("conv3x3_wgrad", conv3x3_wgrad);
   m.impl("linear_wgrad", linear_wgrad);
   m.impl("attn_fwd", attn_fwd);

@@ -31,9 +31,15 @@ HAS = {"joint_groupnorm", "pose_embedding", "frame_conv3x3", "attention",
 
 def conv_shapes_supported(cin: int, cout: int, stride: int) -> bool:
     """The implicit-GEMM kernel covers the FLOP-dominant convs (stride 1,
-    Cin%64==0, Cout%128==0); stem (3ch), strided pose-emb (144ch), head
-    (3ch) and small-config convs take the im2col + hipBLASLt GEMM route."""
+    Cin%64==0, Cout%128==0); stem (3ch), strided pose-emb (144ch) and head
+    (3ch) take the im2col + hipBLASLt GEMM route."""
     return stride == 1 and cin % 64 == 0 and cout % 128 == 0
+
+
+def conv_halo_shapes_supported(cin: int, cout: int, stride: int) -> bool:
+    """The halo-tile kernel (conv3x3_halo.hip) covers the narrow convs of the
+    small config; frame_conv3x3 sends it only what no igemm route takes."""
+    return stride == 1 and cin % 32 == 0 and cout % 32 == 0 and cout <= 128
 
 
 # ---------------------------------------------------------------------------
@@ -220,15 +226,19 @@ def fused_adam_recipe_step(plan: AdamPlan, lr, b1, b2, eps, step: int,
 # im2col + hipBLASLt GEMMs. MIOpen is used nowhere.
 # ---------------------------------------------------------------------------
 
-def _conv_dgrad(dy, w):
-    """dx of a stride-1 conv: conv3x3(dy, w~) with
-    w~[ci,ey,ex,co] = w[co,2-ey,2-ex,ci], on the MFMA kernel when it covers
-    the transposed shape, else by im2col of dy + one GEMM."""
+def _conv_dgrad(dy, w, out_scale=1.0):
+    """out_scale times the dx of a stride-1 conv: conv3x3(dy, w~) with
+    w~[ci,ey,ex,co] = w[co,2-ey,2-ex,ci], on the MFMA kernel (igemm, else
+    halo-tile) that covers the transposed shape, else by im2col of dy + one
+    GEMM."""
     cout, _, _, cin = w.shape
     wt = torch.flip(w, dims=(1, 2)).permute(3, 1, 2, 0).contiguous()
     if conv_shapes_supported(cout, cin, 1):
-        return _OPS.conv3x3_fwd(dy, wt, None, None, 1.0)
-    return _gemm_conv_fwd(dy, wt, None, 1)
+        return _OPS.conv3x3_fwd(dy, wt, None, None, out_scale)
+    if conv_halo_shapes_supported(cout, cin, 1):
+        return _OPS.conv3x3_halo_fwd(dy, wt, None, None, out_scale)
+    dx = _gemm_conv_fwd(dy, wt, None, 1)
+    return dx if out_scale == 1.0 else dx * out_scale
 
 
 class _FrameConv3x3(torch.autograd.Function):
@@ -347,7 +357,7 @@ def _pad_c8(t):
 
 def _gemm_conv_fwd(x, w, bias, stride):
     """Generic 3x3 SAME conv for shapes the MFMA igemm kernel doesn't take
-    (stem 3ch, pose-emb 144ch strided, head 3ch, small configs): strided
+    (stem 3ch, pose-emb 144ch strided, head 3ch): strided
     im2col kernel + ONE hipBLASLt GEMM. Replaces MIOpen entirely."""
     cout, _, _, cin = w.shape
     xp = _pad_c8(x.contiguous())
@@ -364,6 +374,61 @@ def _gemm_conv_fwd(x, w, bias, stride):
     H, W = x.shape[-3], x.shape[-2]
     Ho, Wo = -(-H // stride), -(-W // stride)
     return y.reshape(*x.shape[:-3], Ho, Wo, cout)
+
+
+def _wgrad_im2col9(x, w, dy, has_bias, stride, need_w=True):
+    """Conv wgrad as one GEMM on the 9-plane im2col of x."""
+    cout, _, _, cin = w.shape
+    dyf = dy.reshape(-1, cout)
+    dw = None
+    if need_w:
+        xp = _pad_c8(x)
+        cpad = xp.shape[-1]
+        A = _OPS.im2col3x3(xp, stride, 9, 0, -1, None)
+        dwf = torch.matmul(A.transpose(0, 1), dyf)    # (9*Cpad, Cout)
+        dw = (dwf.reshape(3, 3, cpad, cout)[:, :, :cin, :]
+              .permute(3, 0, 1, 2).contiguous())
+    db = (dyf.sum(0, dtype=torch.float32).to(dy.dtype)
+          if has_bias else None)
+    return dw, db
+
+
+class _FrameConvHalo(torch.autograd.Function):
+    """Halo-tile MFMA conv (narrow channels) with the optionally fused
+    residual tail of _FrameConv3x3. dgrad is the same kernel wherever the
+    transposed shape is eligible; there is no narrow wgrad kernel yet, so
+    wgrad stays the 9-plane im2col GEMM these shapes have always used."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x, weight, bias, residual, res_scale):
+        x = x.contiguous()
+        weight = weight.contiguous()
+        if residual is not None:
+            residual = residual.contiguous()
+        y = _OPS.conv3x3_halo_fwd(x, weight, bias, residual, res_scale)
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        ctx.has_res = residual is not None
+        ctx.res_scale = res_scale
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            # the tail's scale rides in the dgrad epilogue: one rounding
+            dx = _conv_dgrad(dy, w, ctx.res_scale)
+        if ctx.res_scale != 1.0:
+            dy = dy * ctx.res_scale
+        if ctx.needs_input_grad[1] or ctx.has_bias:
+            dw, db = _wgrad_im2col9(x, w, dy, ctx.has_bias, 1,
+                                    ctx.needs_input_grad[1])
+        dres = dy if ctx.has_res else None
+        return dx, dw, db, dres, None
 
 
 class _FrameConvGeneric(torch.autograd.Function):
@@ -386,23 +451,13 @@ class _FrameConvGeneric(torch.autograd.Function):
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
         dy = dy.contiguous()
-        cout, _, _, cin = w.shape
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             assert ctx.stride == 1, "strided dgrad not needed by the model"
             dx = _conv_dgrad(dy, w)
         if ctx.needs_input_grad[1] or ctx.has_bias:
-            dyf = dy.reshape(-1, cout)
-            xp = _pad_c8(x)
-            cpad = xp.shape[-1]
-            A = _OPS.im2col3x3(xp, ctx.stride, 9, 0, -1, None)
-            dwf = torch.matmul(A.transpose(0, 1), dyf)    # (9*Cpad, Cout)
-            dw = (dwf.reshape(3, 3, cpad, cout)[:, :, :cin, :]
-                  .permute(3, 0, 1, 2).contiguous())
-            if not ctx.needs_input_grad[1]:
-                dw = None
-            db = (dyf.sum(0, dtype=torch.float32).to(dy.dtype)
-                  if ctx.has_bias else None)
+            dw, db = _wgrad_im2col9(x, w, dy, ctx.has_bias, ctx.stride,
+                                    ctx.needs_input_grad[1])
         return dx, dw, db, None
 
 
@@ -419,15 +474,20 @@ def frame_conv3x3(x, weight, bias, stride: int = 1):
         xp = Fn.pad(x, (0, pad))
         wp = Fn.pad(weight, (0, pad))
         return _FrameConv3x3.apply(xp, wp, bias, None, 1.0)
+    if conv_halo_shapes_supported(cin, cout, stride):
+        return _FrameConvHalo.apply(x, weight, bias, None, 1.0)
     return _FrameConvGeneric.apply(x, weight, bias, stride)
 
 
 def frame_conv3x3_residual(x, weight, bias, residual, res_scale):
     """y = (conv3x3(x,w) + bias + residual) * res_scale, residual fused in
-    the conv epilogue when the MFMA kernel covers the shape."""
+    the conv epilogue when an MFMA kernel covers the shape."""
     cout, _, _, cin = weight.shape
     if conv_shapes_supported(cin, cout, 1):
         return _FrameConv3x3.apply(x, weight, bias, residual, res_scale)
+    if (conv_halo_shapes_supported(cin, cout, 1)
+            and not (cout % 128 == 0 and cin >= 64)):  # zero-pad igemm route
+        return _FrameConvHalo.apply(x, weight, bias, residual, res_scale)
     y = frame_conv3x3(x, weight, bias, 1)
     return (y + residual) * res_scale
 

@@ -111,8 +111,81 @@ def bench_pose():
                       "ms": round(tms, 3)}), flush=True)
 
 
+def bench_conv_halo(out_path="profiles/conv_halo_bench.jsonl"):
+    """Halo-tile conv against the route it replaces (im2col + hipBLASLt GEMM
+    + eager tail) on the small config's shapes at batch 128: the two
+    alternate in one process, three windows of >= 0.3 s each after warm-up.
+    FLOPs and the HBM bytes the algorithm needs (x, w, y, residual once) are
+    computed from the shapes; `bound` says which of the two peaks (2.5 PF/s
+    bf16 dense, 8 TB/s) gives the larger least time."""
+    import math
+    from novel_view_synthesis_3d_amd.ops import hip_ops
+    shapes = [(128, 2, 64, 64, 32, 32), (128, 2, 64, 64, 96, 32),
+              (128, 2, 64, 64, 64, 32), (128, 2, 32, 32, 32, 64),
+              (128, 2, 32, 32, 64, 64), (128, 2, 32, 32, 96, 64),
+              (128, 2, 32, 32, 128, 64)]
+    rs2 = 1.0 / math.sqrt(2.0)
+
+    def window(fn, min_s=0.3):
+        n, t0 = 0, time.perf_counter()
+        while True:
+            for _ in range(10):
+                fn()
+            n += 10
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            if dt >= min_s:
+                return dt / n * 1000  # ms
+
+    with open(out_path, "w") as f, torch.no_grad():
+        for B, F, H, W, Ci, Co in shapes:
+            x = torch.randn(B, F, H, W, Ci, device="cuda",
+                            dtype=torch.bfloat16)
+            w = torch.randn(Co, 3, 3, Ci, device="cuda",
+                            dtype=torch.bfloat16) * 0.05
+            b = torch.randn(Co, device="cuda", dtype=torch.bfloat16)
+            res = torch.randn(B, F, H, W, Co, device="cuda",
+                              dtype=torch.bfloat16)
+            px = B * F * H * W
+            flops = 2.0 * px * 9 * Ci * Co
+            for tail in (False, True):
+                if tail:
+                    new = lambda: torch.ops.nvs3d.conv3x3_halo_fwd(
+                        x, w, b, res, rs2)
+                    old = lambda: (hip_ops._gemm_conv_fwd(x, w, b, 1)
+                                   + res) * rs2
+                else:
+                    new = lambda: torch.ops.nvs3d.conv3x3_halo_fwd(
+                        x, w, b, None, 1.0)
+                    old = lambda: hip_ops._gemm_conv_fwd(x, w, b, 1)
+                nbytes = 2.0 * (px * (Ci + Co * (2 if tail else 1))
+                                + 9 * Ci * Co)
+                for fn in (new, old):
+                    for _ in range(5):
+                        fn()
+                torch.cuda.synchronize()
+                wins = {"halo": [], "route": []}
+                for _ in range(3):
+                    wins["halo"].append(round(window(new), 4))
+                    wins["route"].append(round(window(old), 4))
+                t = min(wins["halo"])
+                rec = {"op": "conv3x3_halo_fwd",
+                       "shape": [B, F, H, W, Ci, Co], "tail": tail,
+                       "halo_ms": wins["halo"], "route_ms": wins["route"],
+                       "speedup_min": round(min(wins["route"]) / t, 2),
+                       "halo_tflops": round(flops / t / 1e9, 1),
+                       "halo_tb_s": round(nbytes / t / 1e9, 2),
+                       "bound": ("flops" if flops / 2.5e15 > nbytes / 8e12
+                                 else "bytes")}
+                f.write(json.dumps(rec) + "\n")
+                print(json.dumps(rec), flush=True)
+
+
 if __name__ == "__main__":
     assert torch.cuda.is_available()
+    if "--conv-halo" in sys.argv:
+        bench_conv_halo()
+        sys.exit(0)
     bench_conv()
     bench_attn()
     bench_gn()
