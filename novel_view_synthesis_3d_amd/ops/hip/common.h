@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <vector>
+
 #define NVS_WAVE 64
 
 using bf16 = __hip_bfloat16;
@@ -92,7 +94,14 @@ static inline int ceil_div_host(long a, long b) {
   return static_cast<int>((a + b - 1) / b);
 }
 
-#define NVS_CHECK_HIP(expr)                                        \
+// Launcher of conv3x3_wgrad_narrow.hip, reached from the host function of
+// the conv3x3_wgrad op (conv3x3_wgrad.hip); returns {dw} or {dw, db}, fp32.
+namespace at { class Tensor; }
+std::vector<at::Tensor> conv3x3_wgrad_narrow(const at::Tensor& x,
+                                             const at::Tensor& dy,
+                                             bool with_bias);
+
+#define NVS_CHECK_HIP(expr)                                       \
   do {                                                             \
     hipError_t _e = (expr);                                        \
     TORCH_CHECK(_e == hipSuccess, "HIP error: ",                   \

@@ -283,6 +283,13 @@ std::vector<torch::Tensor> conv3x3_wgrad(torch::Tensor x, torch::Tensor dy,
   s.H = xs[nd - 3]; s.W = xs[nd - 2]; s.Cin = xs[nd - 1];
   s.Cout = dy.size(nd - 1);
   TORCH_CHECK(dy.numel() == (long)s.IMG * s.H * s.W * s.Cout);
+  // this kernel's shapes first; the narrow channels of the small config go
+  // to conv3x3_wgrad_narrow.hip (any H, W); everything else raises below
+  const bool wide = s.Cin % WBN == 0 && s.Cout % WBM == 0 && s.W % 16 == 0 &&
+                    (s.W <= 128 || s.W % 128 == 0);
+  if (!wide && s.Cin % 32 == 0 && s.Cout % 32 == 0 && s.Cout <= 128) {
+    return conv3x3_wgrad_narrow(x, dy, with_bias);
+  }
   TORCH_CHECK(s.Cin % WBN == 0 && s.Cout % WBM == 0);
   TORCH_CHECK(s.W % 16 == 0 && (s.W <= 128 || s.W % 128 == 0));
 

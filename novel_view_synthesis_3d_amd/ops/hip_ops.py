@@ -221,9 +221,10 @@ def fused_adam_recipe_step(plan: AdamPlan, lr, b1, b2, eps, step: int,
 
 
 # ---------------------------------------------------------------------------
-# 3x3 conv (K1): fwd + dgrad on the implicit-GEMM MFMA kernel, wgrad on the
-# direct MFMA wgrad kernel; shapes those kernels do not cover go through
-# im2col + hipBLASLt GEMMs. MIOpen is used nowhere.
+# 3x3 conv (K1): fwd + dgrad on the implicit-GEMM or halo-tile MFMA kernel,
+# wgrad on the direct MFMA wgrad kernels (wide and narrow channels); shapes
+# those kernels do not cover go through im2col + hipBLASLt GEMMs. MIOpen is
+# used nowhere.
 # ---------------------------------------------------------------------------
 
 def _conv_dgrad(dy, w, out_scale=1.0):
@@ -396,8 +397,9 @@ def _wgrad_im2col9(x, w, dy, has_bias, stride, need_w=True):
 class _FrameConvHalo(torch.autograd.Function):
     """Halo-tile MFMA conv (narrow channels) with the optionally fused
     residual tail of _FrameConv3x3. dgrad is the same kernel wherever the
-    transposed shape is eligible; there is no narrow wgrad kernel yet, so
-    wgrad stays the 9-plane im2col GEMM these shapes have always used."""
+    transposed shape is eligible; wgrad is the conv3x3_wgrad op, which sends
+    these channel counts to conv3x3_wgrad_narrow.hip at any image size
+    (NVS3D_WGRAD=im2col keeps the 9-plane im2col GEMM)."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
@@ -422,9 +424,20 @@ class _FrameConvHalo(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # the tail's scale rides in the dgrad epilogue: one rounding
             dx = _conv_dgrad(dy, w, ctx.res_scale)
+        direct = (ctx.needs_input_grad[1]
+                  and os.environ.get("NVS3D_WGRAD", "mfma") != "im2col")
+        if direct:
+            # on the unscaled dy; the tail's scale multiplies the 36 KB fp32
+            # results, so dw and db are rounded to bf16 once
+            outs = _OPS.conv3x3_wgrad(x, dy, ctx.has_bias)
+            if ctx.res_scale != 1.0:
+                outs = [o * ctx.res_scale for o in outs]
+            dw = outs[0].to(x.dtype)
+            db = outs[1].to(dy.dtype) if ctx.has_bias else None
         if ctx.res_scale != 1.0:
             dy = dy * ctx.res_scale
-        if ctx.needs_input_grad[1] or ctx.has_bias:
+        if not direct and (ctx.needs_input_grad[1] or ctx.has_bias):
+            # the old route, or the bias sum alone
             dw, db = _wgrad_im2col9(x, w, dy, ctx.has_bias, 1,
                                     ctx.needs_input_grad[1])
         dres = dy if ctx.has_res else None

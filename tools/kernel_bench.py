@@ -181,10 +181,72 @@ def bench_conv_halo(out_path="profiles/conv_halo_bench.jsonl"):
                 print(json.dumps(rec), flush=True)
 
 
+def bench_conv_wgrad_narrow(out_path="profiles/conv_wgrad_narrow_bench.jsonl"):
+    """Narrow direct wgrad (the conv3x3_wgrad op) against the route it
+    replaces (`_wgrad_im2col9`: 9-plane im2col + one hipBLASLt GEMM + the bias
+    sum) on the small config's shapes at batch 128, with bias: the two
+    alternate in one process, three windows of >= 0.3 s each after warm-up.
+    TB/s counts x and dy once, TF/s 2*9*Cin*Cout per pixel, both over the
+    kernel route's time."""
+    from novel_view_synthesis_3d_amd.ops import hip_ops
+    shapes = [(128, 2, 64, 64, 32, 32), (128, 2, 64, 64, 96, 32),
+              (128, 2, 64, 64, 64, 32), (128, 2, 32, 32, 32, 64),
+              (128, 2, 32, 32, 64, 64), (128, 2, 32, 32, 96, 64),
+              (128, 2, 32, 32, 128, 64)]
+
+    def window(fn, min_s=0.3):
+        n, t0 = 0, time.perf_counter()
+        while True:
+            for _ in range(10):
+                fn()
+            n += 10
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            if dt >= min_s:
+                return dt / n * 1000  # ms
+
+    with open(out_path, "w") as f, torch.no_grad():
+        for B, F, H, W, Ci, Co in shapes:
+            x = torch.randn(B, F, H, W, Ci, device="cuda",
+                            dtype=torch.bfloat16)
+            dy = torch.randn(B, F, H, W, Co, device="cuda",
+                             dtype=torch.bfloat16)
+            w = torch.empty(Co, 3, 3, Ci, device="cuda",
+                            dtype=torch.bfloat16)
+            px = B * F * H * W
+            flops = 2.0 * px * 9 * Ci * Co
+            nbytes = 2.0 * px * (Ci + Co)
+            new = lambda: torch.ops.nvs3d.conv3x3_wgrad(x, dy, True)
+            old = lambda: hip_ops._wgrad_im2col9(x, w, dy, True, 1)
+            for fn in (new, old):
+                for _ in range(5):
+                    fn()
+            torch.cuda.synchronize()
+            dw_n, dw_o = new()[0], old()[0].float()
+            rel = ((dw_n - dw_o).norm() / dw_n.norm()).item()
+            wins = {"narrow": [], "route": []}
+            for _ in range(3):
+                wins["narrow"].append(round(window(new), 4))
+                wins["route"].append(round(window(old), 4))
+            t = min(wins["narrow"])
+            rec = {"op": "conv3x3_wgrad_narrow",
+                   "shape": [B, F, H, W, Ci, Co],
+                   "narrow_ms": wins["narrow"], "route_ms": wins["route"],
+                   "speedup_min": round(min(wins["route"]) / t, 2),
+                   "narrow_tb_s": round(nbytes / t / 1e9, 2),
+                   "narrow_tflops": round(flops / t / 1e9, 1),
+                   "rel_l2_vs_route": float(f"{rel:.3e}")}
+            f.write(json.dumps(rec) + "\n")
+            print(json.dumps(rec), flush=True)
+
+
 if __name__ == "__main__":
     assert torch.cuda.is_available()
     if "--conv-halo" in sys.argv:
         bench_conv_halo()
+        sys.exit(0)
+    if "--conv-wgrad-narrow" in sys.argv:
+        bench_conv_wgrad_narrow()
         sys.exit(0)
     bench_conv()
     bench_attn()
